@@ -18,7 +18,15 @@ Inputs (images, boxes, token ids) and all weights are resident in HBM before the
 environment).  Multi-GPU: the path shards by image with no data-path collective (inference
 replicas), so scaling is weak and `value` = all ranks' region tokens / max-rank time.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the `--steps` steps and prints the line.  Everything else moves behind `--full`
+(off by default): the serial timing beside the headline, the finite-logits check, the extra objects below, the decode,
+greedy-parity, extras and training legs, the other storage type and the CPU baseline.  Their `--no-*` / `--*-steps` /
+`--*-tokens` switches still apply under `--full`.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller (the fp32 logits [batch, T, vocab]) as
+DIR/<name>.npy: the last position of every request and a fixed seeded sample of rows, < 64 MB in all (dump_outputs).
+
+Extra objects on the JSON line (`--full`):
   roofline     -- the kernel family with the largest share of a step, timed per launch with HIP
                   events on the launch stream in an instrumented (untimed) extra step
   cpu_baseline -- the reference's CPU path for the stages north_star names (mmcv CPU RoIAlign as
@@ -96,6 +104,12 @@ def parse():
                          "LlamaForCausalLM fp32 built from the same weights, from the path's own prompt embeddings; 0 = skip")
     ap.add_argument("--decode-tokens", type=int, default=32,
                     help="extra (not part of `value`): greedy KV-cache decode steps timed after the prefill")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline (serial timing, logits check, roofline, decode, greedy parity, "
+                         "extras, training legs, the other storage type, CPU baseline); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's logits (every request's last position + a seeded "
+                         "sample of rows) as DIR/<name>.npy, float32")
     return ap.parse_args()
 
 
@@ -141,6 +155,22 @@ def make_inputs(args, ids, device, seed, batch=None, image_size=None):
     boxes = [syn.boxes(args.rois, g).to(device) for _ in range(B)]
     prompt = torch.stack([syn.prompt_ids(ids, P, args.rois, g) for _ in range(B)]).to(device)
     return image, boxes, prompt
+
+
+def dump_outputs(path, logits, seed=0):
+    """--dump-outputs: the fp32 logits [B, T, V] one step returns, as float32 .npy files of at most 30 MiB each.  The whole
+    tensor is 1.6 GB at the headline shape, so: logits_last = the last position of every request (the next-token
+    distribution; the first rows that fit), logits_rows = a fixed seeded sample of (request, position) rows over the whole
+    tensor, logits_rows_index = their flat row indices b * T + t (float64)."""
+    import numpy as np
+    B, T, V = logits.shape
+    cap = max(1, (30 << 20) // (4 * V))
+    idx = np.sort(np.random.default_rng(seed).choice(B * T, size=min(B * T, cap), replace=False))
+    rows = logits.reshape(B * T, V)[torch.as_tensor(idx, device=logits.device)]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "logits_last.npy"), logits[:cap, -1].float().cpu().numpy())
+    np.save(os.path.join(path, "logits_rows.npy"), rows.float().cpu().numpy())
+    np.save(os.path.join(path, "logits_rows_index.npy"), idx.astype(np.float64))
 
 
 def timed_replay(model, image, boxes, prompt, steps, warmup=2, streams=1, attention_mask=None):
@@ -559,7 +589,7 @@ def main():
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, stream=st):
-                    last["graph_out_%d" % i] = eager(i)
+                    last["out_%d" % i] = eager(i)                 # every replay rewrites this tensor
                 graphs[i] = g
             torch.cuda.synchronize()
         except Exception as ex:                                   # keep the bench alive; say so in the JSON
@@ -574,7 +604,7 @@ def main():
             if graphs[i] is not None:
                 graphs[i].replay()
             else:
-                eager(i)
+                last["out_%d" % i] = eager(i)
 
     def serial_step():
         model(input_ids=prompt, images=image, bboxes=reqs[0])
@@ -589,15 +619,20 @@ def main():
     dt_local = replicas.timed_steps(step, args.steps, torch.cuda.synchronize, dist)
     device_allocs_in_timed_region = torch.cuda.memory_stats(device).get("num_device_alloc", 0) - seg0
     _, dt = replicas.aggregate(args.rois * args.batch * args.steps, dt_local, dist, device=device if backend == "nccl" else "cpu")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last["out_%d" % ((counter["i"] - 1) % len(ctxs))])
     # the same K steps strictly serial on one stream (per-image latency), reported beside the headline
-    serial_step()
-    dt_serial = replicas.timed_steps(serial_step, args.steps, torch.cuda.synchronize, dist) if len(ctxs) > 1 else dt_local
-    logits = model(input_ids=prompt, images=image, bboxes=boxes)
-    assert torch.isfinite(logits[0, -1]).all(), "non-finite logits"
-    del logits
+    dt_serial = dt_local if len(ctxs) == 1 else None
+    if args.full:
+        serial_step()
+        if len(ctxs) > 1:
+            dt_serial = replicas.timed_steps(serial_step, args.steps, torch.cuda.synchronize, dist)
+        logits = model(input_ids=prompt, images=image, bboxes=boxes)
+        assert torch.isfinite(logits[0, -1]).all(), "non-finite logits"
+        del logits
 
     roofline, kernels = None, None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         K.PROFILER.start()
         serial_step()
         agg = K.PROFILER.stop()
@@ -723,7 +758,7 @@ def main():
                                                  else None)(pmc_rec("roi_align_mlvl_nhwc") if counters_ok else {})}
 
     decode = None
-    if rank == 0 and args.decode_tokens > 0:
+    if rank == 0 and args.full and args.decode_tokens > 0:
         # configs[1] continues with greedy decode from the KV cache; reported beside the headline,
         # never inside it (weight-streaming bound: 13.5 GB of bf16 weights per token)
         emb = model.embed_inputs(prompt[:1], image[:1], model.prepare_boxes(boxes[:1], args.image_size))
@@ -770,7 +805,7 @@ def main():
             decode["batched"] = {"error": repr(ex)}
 
     live_parity = None
-    if rank == 0 and world == 1 and args.parity_tokens > 0:
+    if rank == 0 and world == 1 and args.full and args.parity_tokens > 0:
         try:
             live_parity = live_parity_leg(args, model, image, boxes, prompt, device)
         except Exception as ex:                                      # never lose the headline
@@ -778,7 +813,7 @@ def main():
             torch.cuda.empty_cache()
 
     vit = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         try:
             vit = vit_roofline(model, args, device)
         except Exception as ex:
@@ -786,7 +821,7 @@ def main():
         if roofline is not None:
             roofline["vit"] = vit
     extras = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         # extra legs, never part of `value`: (a) ONE batch-1 request, strictly serial (the per-request latency of configs[1]);
         # (b) the reference-native 224^2 resolution (its RoI extractor asserts a 16 x 16 grid, layers.py:289-291), same merge;
         # (c) the same merged launch sequence in the reference's SERVING dtype (fp16, app.py:74-98) when the headline is bf16
@@ -849,7 +884,7 @@ def main():
     other_name = "bf16" if args.dtype == "fp16" else "fp16"
     other_dtype = torch.bfloat16 if other_name == "bf16" else torch.float16
     want_other_leg = rank == 0 and extras is not None and world == 1
-    want_train = args.train_steps > 0
+    want_train = args.full and args.train_steps > 0
     del graphs, ctxs, reqs                               # release the captured inference pools
     graph_error = last.get("graph_error")
     last.clear()
@@ -907,14 +942,14 @@ def main():
         m2 = None
         torch.cuda.empty_cache()
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(args)
         except Exception as ex:                                      # never lose the GPU number
             cpu = {"error": repr(ex)}
 
     greedy = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # exact-id statistics of the committed GPU test for this storage type: written by
         # tests/test_fullwidth_gpu.py on the GPU box, merged into profiles/rNN_greedy_parity.json
         try:
@@ -971,8 +1006,9 @@ def main():
             "in_flight_requests_per_gpu": n_ctx, "hipMalloc_calls_in_timed_region": device_allocs_in_timed_region,
             "hipgraph": graph_ok, "hipgraph_error": last.get("graph_error"),
             "requests_per_step": args.batch,
-            "single_stream": {"ms_per_image": round(1e3 * dt_serial / args.steps / args.batch, 3),
-                              "region_tokens_per_s_per_gpu": round(args.rois * args.batch * args.steps / dt_serial, 2)},
+            "single_stream": None if dt_serial is None else {
+                "ms_per_image": round(1e3 * dt_serial / args.steps / args.batch, 3),
+                "region_tokens_per_s_per_gpu": round(args.rois * args.batch * args.steps / dt_serial, 2)},
             "config": {"workload": f"configs[1]: batch-1 requests of 1x{args.image_size}^2 image + {args.rois} RoIs, {args.batch} of them "
                                    f"merged per launch sequence: ViT-L/14(23 blocks) + SPI(P={P}) + LLaMA-7B({args.llama_layers} "
                                    f"layers) prefill T={prompt.size(1)} per request with full logits",

@@ -12,6 +12,8 @@ Outputs (committed, small):
                         fractional scales 1/1.75..1/14, gpt4roi/models/layers.py:206-214)
                         plus the edge cases; outputs/gradients produced by oracle/_ref =
                         the reference's own CPU implementation compiled unmodified.
+                        The case lvl0 is in roi_align_seeded_lvl0.npz (each file < 1 MiB).
+  roi_align_ref_agree.npz  one case with the compiled reference op's output (ref_agree).
 """
 import os
 import sys
@@ -98,7 +100,9 @@ def seeded():
     gi = O.ref_backward(g, r, x.shape, 14, 1.0, 2, "avg", True)
     d.update({"edges.x": x, "edges.rois": r, "edges.out": o, "edges.gout": g, "edges.gin": gi,
               "edges.cfg": np.array([14, 14, 2, 1, 1], np.int64), "edges.scale": np.array(1.0)})
-    np.savez_compressed(os.path.join(HERE, "roi_align_seeded.npz"), **d)
+    # two files, each under the 1 MiB a committed file may take: the largest case (lvl0) in a file of its own
+    np.savez_compressed(os.path.join(HERE, "roi_align_seeded_lvl0.npz"), **{k: v for k, v in d.items() if k.startswith("lvl0.")})
+    np.savez_compressed(os.path.join(HERE, "roi_align_seeded.npz"), **{k: v for k, v in d.items() if not k.startswith("lvl0.")})
 
 
 def edges_mlvl():
@@ -125,9 +129,21 @@ def edges_mlvl():
     np.savez_compressed(os.path.join(HERE, "roi_align_edges_mlvl.npz"), **d)
 
 
+def ref_agree():
+    """The case of tests/test_oracle_roi_align.py::test_ref_build_agrees_when_present with the reference's compiled CPU op's
+    output recorded, so that the test needs no oracle/_ref."""
+    rng = np.random.default_rng(3)
+    x = rng.standard_normal((2, 4, 24, 24)).astype(np.float32)
+    r = np.array([[0, 3.3, 4.1, 60.2, 70.9], [1, 10., 10., 50., 30.], [1, 0., 0., 96., 96.]], np.float32)
+    out = O.ref_forward(x, r, 14, 0.25, 2)[0]
+    np.savez_compressed(os.path.join(HERE, "roi_align_ref_agree.npz"), x=x, rois=r, out=out)
+
+
 if __name__ == "__main__":
     known()
     seeded()
     edges_mlvl()
-    for f in ("roi_align_known.npz", "roi_align_seeded.npz", "roi_align_edges_mlvl.npz"):
+    ref_agree()
+    for f in ("roi_align_known.npz", "roi_align_seeded.npz", "roi_align_seeded_lvl0.npz", "roi_align_edges_mlvl.npz",
+              "roi_align_ref_agree.npz"):
         print(f, os.path.getsize(os.path.join(HERE, f)), "bytes")

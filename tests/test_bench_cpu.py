@@ -106,3 +106,23 @@ def test_greedy_record_merger(tmp_path, monkeypatch):
     spec.loader.exec_module(importlib.util.module_from_spec(spec))
     doc = json.load(open(root / "profiles" / "r07_greedy_parity.json"))
     assert [r["dtype"] for r in doc["runs"]] == ["bf16", "fp16"] and doc["merged16"]["merged_exact_len"][-1] == 40
+
+
+def test_dump_outputs_writes_a_fixed_sample_of_the_logits(bench, tmp_path):
+    """--dump-outputs: every request's last-position logits + a seeded sample of rows with their flat indices, float32 /
+    float64, the same files for the same tensor; a vocabulary too wide for the size cap gets fewer rows"""
+    import numpy as np
+    import torch
+    logits = torch.randn(3, 5, 7, generator=torch.Generator().manual_seed(0))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), logits)
+    for f in ("logits_last.npy", "logits_rows.npy", "logits_rows_index.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    last, rows, idx = (np.load(tmp_path / "a" / f) for f in ("logits_last.npy", "logits_rows.npy", "logits_rows_index.npy"))
+    assert last.dtype == rows.dtype == np.float32 and idx.dtype == np.float64
+    assert np.array_equal(last, logits[:, -1].numpy())
+    assert sorted(idx.astype(int).tolist()) == list(range(15))                  # small enough: every row
+    assert np.array_equal(rows, logits.reshape(15, 7).numpy()[idx.astype(int)])
+    wide = torch.zeros(2, 1, (30 << 20) // 4 // 2 + 1)                               # two rows no longer fit in 30 MiB
+    bench.dump_outputs(str(tmp_path / "w"), wide)
+    assert np.load(tmp_path / "w" / "logits_rows.npy").shape[0] == 1 and np.load(tmp_path / "w" / "logits_last.npy").shape[0] == 1

@@ -13,7 +13,9 @@ from oracle import roi_align as O
 
 
 def _cases(golden_dir):
-    z = np.load(os.path.join(golden_dir, "roi_align_seeded.npz"))
+    z = {}
+    for f in ("roi_align_seeded.npz", "roi_align_seeded_lvl0.npz"):      # (one fixture in two files, each < 1 MiB)
+        z.update(np.load(os.path.join(golden_dir, f)))
     return z, [str(n) for n in z["names"]]
 
 
@@ -74,15 +76,15 @@ def test_empty_rois():
     assert out.shape == (0, 2, 14, 14)
 
 
-def test_ref_build_agrees_when_present():
-    if O.load_ref() is None:
-        pytest.skip("oracle/_ref not built in this checkout")
-    rng = np.random.default_rng(3)
-    x = rng.standard_normal((2, 4, 24, 24)).astype(np.float32)
-    r = np.array([[0, 3.3, 4.1, 60.2, 70.9], [1, 10., 10., 50., 30.], [1, 0., 0., 96., 96.]], np.float32)
+def test_ref_build_agrees_when_present(golden_dir):
+    # against the reference op's recorded output (tests/golden/make_golden.py::ref_agree), and live when oracle/_ref is built
+    z = np.load(os.path.join(golden_dir, "roi_align_ref_agree.npz"))
+    x, r = z["x"], z["rois"]
     a = O.forward(x, r, 14, 0.25, 2)[0]
-    b = O.ref_forward(x, r, 14, 0.25, 2)[0]
-    assert np.array_equal(a, b)
+    assert np.array_equal(a, z["out"])
+    if O.load_ref() is not None:
+        b = O.ref_forward(x, r, 14, 0.25, 2)[0]
+        assert np.array_equal(a, b)
 
 
 def test_random_configurations_against_the_compiled_reference_and_adjoint():
