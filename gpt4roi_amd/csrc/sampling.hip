@@ -39,20 +39,26 @@ constexpr int LIST_CAP = 1024;
 // six passes over it (max, four radix-select passes, gather) read it from there; the first version walked the row in
 // global memory with 256 threads, ~140 us per token.
 constexpr int SNT = 1024;
-__global__ __launch_bounds__(SNT) void sample_advance_kernel(const float* __restrict__ glogits, int N, int in_lds, float inv_temp,
-                                                             int top_k, float top_p,
-                                                             const unsigned long long* __restrict__ seed,
-                                                             long* __restrict__ tok, long* __restrict__ out_ids,
-                                                             int* __restrict__ step, int* __restrict__ pos,
-                                                             int max_steps, float* __restrict__ u_out) {
-  extern __shared__ __attribute__((aligned(16))) float staged[];
-  __shared__ float red[SNT];
-  __shared__ unsigned hist[256];
-  __shared__ unsigned sel_prefix, sel_mask, sel_k, list_n;
-  __shared__ int list_idx[LIST_CAP];
-  __shared__ float list_e[LIST_CAP];
-  __shared__ double chunk_sum[256];
+
+struct SampleLds {                         // the static LDS of one draw (~15 KB)
+  float red[SNT];
+  unsigned hist[256];
+  unsigned sel_prefix, sel_mask, sel_k, list_n;
+  int list_idx[LIST_CAP];
+  float list_e[LIST_CAP];
+  double chunk_sum[256];
+};
+
+// One draw from the row `glogits[0, N)` with the uniform u: the body of the batch-1 and the batched sampler.  Every thread
+// of the workgroup calls it; the token id is valid in thread 0 only.  `staged`: N floats of dynamic LDS when in_lds.
+__device__ __forceinline__ int sample_row(const float* __restrict__ glogits, int N, int in_lds, float* staged,
+                                          float inv_temp, int top_k, float top_p, float u, SampleLds& sh) {
   const int tid = threadIdx.x;
+  float* red = sh.red;
+  unsigned* hist = sh.hist;
+  int* list_idx = sh.list_idx;
+  float* list_e = sh.list_e;
+  double* chunk_sum = sh.chunk_sum;
   const float* logits = glogits;
   if (in_lds) {
     for (int i = tid; i < N; i += SNT) staged[i] = glogits[i];
@@ -70,12 +76,6 @@ __global__ __launch_bounds__(SNT) void sample_advance_kernel(const float* __rest
   }
   m = red[0];
   __syncthreads();
-  // ---- the uniform of this step ----
-  const int st = *step;
-  uint32_t r4[4];
-  const unsigned long long sd = seed ? *seed : 0ull;
-  philox4x32_10((uint32_t)st, 0u, 0u, 0u, (uint32_t)sd, (uint32_t)(sd >> 32), r4);
-  const float u = (float)(r4[0] >> 8) * (1.0f / 16777216.0f);        // 24-bit uniform in [0, 1)
   int choice = -1;
   const int k_eff = top_k < N ? top_k : N;   // HF: top_k = min(top_k, vocabulary)
   uint32_t kth = 0;                          // order key of the k-th largest logit (0: every token kept)
@@ -83,37 +83,37 @@ __global__ __launch_bounds__(SNT) void sample_advance_kernel(const float* __rest
   if (top_k >= 1 && (k_eff < N || N <= LIST_CAP)) {
     // ---- k-th largest logit by MSB radix select on the order-preserving key (ties with the k-th are all kept, as
     //      HF's TopKLogitsWarper does: scores < kth are removed) ----
-    if (tid == 0) { sel_prefix = 0; sel_mask = 0; sel_k = (unsigned)k_eff; }
+    if (tid == 0) { sh.sel_prefix = 0; sh.sel_mask = 0; sh.sel_k = (unsigned)k_eff; }
     for (int pass = 3; pass >= 0; --pass) {
       if (tid < 256) hist[tid] = 0;
       __syncthreads();
-      const unsigned pre = sel_prefix, msk = sel_mask;
-      const int sh = pass * 8;
+      const unsigned pre = sh.sel_prefix, msk = sh.sel_mask;
+      const int shift = pass * 8;
       for (int i = tid; i < N; i += SNT) {
         const uint32_t k = order_key(logits[i]);
-        if ((k & msk) == pre) atomicAdd(&hist[(k >> sh) & 255u], 1u);
+        if ((k & msk) == pre) atomicAdd(&hist[(k >> shift) & 255u], 1u);
       }
       __syncthreads();
       if (tid == 0) {
-        unsigned cum = 0, k_rem = sel_k;
+        unsigned cum = 0, k_rem = sh.sel_k;
         int b = 255;
         for (; b > 0; --b) {
           if (cum + hist[b] >= k_rem) break;
           cum += hist[b];
         }
-        sel_k = k_rem - cum;
-        sel_prefix = pre | ((unsigned)b << sh);
-        sel_mask = msk | (255u << sh);
+        sh.sel_k = k_rem - cum;
+        sh.sel_prefix = pre | ((unsigned)b << shift);
+        sh.sel_mask = msk | (255u << shift);
       }
       __syncthreads();
     }
-    kth = sel_prefix;
-    if (tid == 0) list_n = 0;
+    kth = sh.sel_prefix;
+    if (tid == 0) sh.list_n = 0;
     __syncthreads();
     for (int i = tid; i < N; i += SNT) {
       const float l = logits[i];
       if (order_key(l) >= kth) {
-        const unsigned slot = atomicAdd(&list_n, 1u);
+        const unsigned slot = atomicAdd(&sh.list_n, 1u);
         if (slot < LIST_CAP) {
           list_idx[slot] = i;
           list_e[slot] = expf((l - m) * inv_temp);
@@ -123,11 +123,11 @@ __global__ __launch_bounds__(SNT) void sample_advance_kernel(const float* __rest
     __syncthreads();
     // more than LIST_CAP tokens tie at the k-th logit (degenerate rows, e.g. constant logits): the kept set does not
     // fit the list -> chunked draw over the tokens with key >= kth below (top_p is not applied in that case)
-    use_list = list_n <= (unsigned)LIST_CAP;
+    use_list = sh.list_n <= (unsigned)LIST_CAP;
     if (use_list) {
       // ascending vocabulary order by rank: entry a goes to slot #{b : idx[b] < idx[a]} (the indices are distinct); one
       // thread per entry instead of thread 0's insertion sort (~30 us at top_k = 50)
-      const int n = (int)list_n;
+      const int n = (int)sh.list_n;
       int my_i = 0, rank = 0;
       float my_e = 0.f;
       if (tid < n) {
@@ -140,7 +140,7 @@ __global__ __launch_bounds__(SNT) void sample_advance_kernel(const float* __rest
       __syncthreads();
     }
     if (use_list && tid == 0) {
-      int n = (int)list_n;
+      int n = (int)sh.list_n;
       double Z = 0.0;
       for (int a = 0; a < n; ++a) Z += (double)list_e[a];
       if (top_p < 1.0f) {
@@ -203,13 +203,79 @@ __global__ __launch_bounds__(SNT) void sample_advance_kernel(const float* __rest
           if (order_key(logits[i]) >= kth) { choice = i; break; }
     }
   }
-  if (tid == 0) {
-    if (choice < 0) choice = 0;
+  return choice < 0 ? 0 : choice;
+}
+
+// The uniform of step `st` for a 64-bit seed: 24 bits of Philox4x32-10(counter = (st,0,0,0), key = seed)[0] in [0, 1).
+__device__ __forceinline__ float step_uniform(int st, unsigned long long sd) {
+  uint32_t r4[4];
+  philox4x32_10((uint32_t)st, 0u, 0u, 0u, (uint32_t)sd, (uint32_t)(sd >> 32), r4);
+  return (float)(r4[0] >> 8) * (1.0f / 16777216.0f);
+}
+
+__global__ __launch_bounds__(SNT) void sample_advance_kernel(const float* __restrict__ glogits, int N, int in_lds, float inv_temp,
+                                                             int top_k, float top_p,
+                                                             const unsigned long long* __restrict__ seed,
+                                                             long* __restrict__ tok, long* __restrict__ out_ids,
+                                                             int* __restrict__ step, int* __restrict__ pos,
+                                                             int max_steps, float* __restrict__ u_out) {
+  extern __shared__ __attribute__((aligned(16))) float staged[];
+  __shared__ SampleLds sh;
+  const int st = *step;
+  const float u = step_uniform(st, seed ? *seed : 0ull);
+  const int choice = sample_row(glogits, N, in_lds, staged, inv_temp, top_k, top_p, u, sh);
+  if (threadIdx.x == 0) {
     tok[0] = choice;
     if (st < max_steps) out_ids[st] = choice;
     if (u_out && st < max_steps) u_out[st] = u;
     *step = st + 1;
     *pos = *pos + 1;
+  }
+}
+
+// Batched draw: workgroup b = row b with its own temperature / top-k / top-p / seed, all read from device memory (one
+// captured graph serves any mix).  temperature[b] <= 0: greedy row, the argmax with the lowest index on ties -- the id
+// g4r_argmax_rows_f32 returns.  Reads *step, never writes it: g4r_batch_advance moves the counters afterwards.
+__global__ __launch_bounds__(SNT) void sample_rows_kernel(const float* __restrict__ glogits, long ld, int N, int in_lds,
+                                                          const float* __restrict__ temperature,
+                                                          const int* __restrict__ top_k, const float* __restrict__ top_p,
+                                                          const unsigned long long* __restrict__ seed,
+                                                          const int* __restrict__ step, long* __restrict__ next_ids,
+                                                          float* __restrict__ u_out, int u_stride) {
+  extern __shared__ __attribute__((aligned(16))) float staged[];
+  __shared__ SampleLds sh;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const float* row = glogits + (size_t)b * ld;
+  const int st = *step;
+  const float u = step_uniform(st, seed[b]);
+  const float t = temperature[b];
+  int choice;
+  if (t <= 0.f) {
+    float best = -INFINITY;
+    int idx = 0x7fffffff;
+    for (int i = tid; i < N; i += SNT) {
+      const float v = row[i];
+      if (v > best || (v == best && i < idx)) { best = v; idx = i; }
+    }
+    sh.red[tid] = best;
+    sh.list_idx[tid] = idx;
+    __syncthreads();
+    for (int s = SNT / 2; s > 0; s >>= 1) {
+      if (tid < s) {
+        const float v = sh.red[tid + s];
+        const int i = sh.list_idx[tid + s];
+        if (v > sh.red[tid] || (v == sh.red[tid] && i < sh.list_idx[tid])) { sh.red[tid] = v; sh.list_idx[tid] = i; }
+      }
+      __syncthreads();
+    }
+    choice = sh.list_idx[0];
+  } else {
+    const int k = min(max(top_k[b], 0), LIST_CAP);
+    choice = sample_row(row, N, in_lds, staged, 1.0f / t, k, top_p[b], u, sh);
+  }
+  if (tid == 0) {
+    next_ids[b] = choice;
+    if (u_out && st < u_stride) u_out[(size_t)b * u_stride + st] = u;
   }
 }
 
@@ -235,5 +301,25 @@ extern "C" int g4r_sample_advance_f32(const float* logits, int N, float temperat
   hipLaunchKernelGGL(sample_advance_kernel, dim3(1), dim3(SNT), lds, (hipStream_t)stream, logits, N, in_lds,
                      1.0f / temperature, top_k, top_p, seed, tok, out_ids, step, pos, max_steps, u_out);
   G4R_CHECK_LAUNCH("sample_advance");
+  return G4R_OK;
+}
+
+extern "C" int g4r_sample_rows_f32(const float* logits, long row_stride, int B, int N, const float* temperature,
+                                   const int* top_k, const float* top_p, const unsigned long long* seed, const int* step,
+                                   long* next_ids, float* u_out, int u_stride, void* stream) {
+  G4R_REQUIRE(logits && temperature && top_k && top_p && seed && step && next_ids, "sample_rows: null pointer");
+  G4R_REQUIRE(B > 0 && N > 0 && row_stride >= N, "sample_rows: B > 0, N > 0, row_stride >= N");
+  G4R_REQUIRE(!u_out || u_stride > 0, "sample_rows: u_stride > 0 with u_out");
+  const int in_lds = (size_t)N * 4 <= 140 * 1024;
+  const size_t lds = in_lds ? (size_t)N * 4 : 0;
+  static G4rPerDeviceOnce attr_set;
+  if (attr_set.first()) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sample_rows_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024);
+    if (e != hipSuccess) { attr_set.failed(); return g4r_note_hip_error(e, "sample_rows: hipFuncSetAttribute"); }
+  }
+  hipLaunchKernelGGL(sample_rows_kernel, dim3(B), dim3(SNT), lds, (hipStream_t)stream, logits, row_stride, N, in_lds,
+                     temperature, top_k, top_p, seed, step, next_ids, u_out, u_stride);
+  G4R_CHECK_LAUNCH("sample_rows");
   return G4R_OK;
 }

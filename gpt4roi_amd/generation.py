@@ -96,6 +96,38 @@ class SamplingConfig:
         return (float(self.temperature), k, float(self.top_p))
 
 
+SEED_STRIDE = 0x9E3779B97F4A7C15       # 2^64 / golden ratio: the seeds of the rows of a batch sampled with one int seed
+
+
+def expand_seeds(seeds, B):
+    """The B per-row Philox keys of a batched sampling call, as ints in [0, 2^64).  seeds = None: B seeds drawn from torch's
+    generator (as batch-1 generate draws its one seed); an int s: row b gets (s + b * SEED_STRIDE) mod 2^64, so row 0 draws
+    the stream of a batch-1 call with seed s; a list / tuple: one seed per row."""
+    if seeds is None:
+        return [int(x) for x in torch.randint(0, 2 ** 62, (B,)).tolist()]
+    if isinstance(seeds, (list, tuple)):
+        if len(seeds) != B:
+            raise ValueError(f"{len(seeds)} seeds for a batch of {B} sequences")
+        return [int(x) % 2 ** 64 for x in seeds]
+    return [(int(seeds) + b * SEED_STRIDE) % 2 ** 64 for b in range(B)]
+
+
+def row_samplers(sampler, B):
+    """Per-row token selection of a batch: None (every row greedy), one (temperature, top_k, top_p) for every row, or a list
+    of B entries, each None (greedy) or a tuple.  -> list of B entries."""
+    if sampler is None or isinstance(sampler, tuple):
+        rows = [sampler] * B
+    else:
+        rows = list(sampler)
+        if len(rows) != B:
+            raise ValueError(f"{len(rows)} samplers for a batch of {B} sequences")
+    for r in rows:
+        if r is not None and (len(r) != 3 or not r[0] > 0 or not 0 < r[2] <= 1.0 or not 0 <= int(r[1]) <= 1024
+                              or (r[2] < 1.0 and int(r[1]) == 0)):
+            raise ValueError(f"sampler {r!r}: (temperature > 0, top_k in [0, 1024], top_p in (0, 1]; top_p < 1 needs top_k)")
+    return rows
+
+
 def dense_or_mask(attention_mask):
     """Training batches: None when the mask is absent, all ones or RIGHT-padded (what the collator produces,
     data_modules.py:22-56) -- causal attention already hides the pad keys from every real row and the pad rows carry no

@@ -73,6 +73,7 @@ _SIGS = {
     "g4r_rope_qkv_bf16": [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P],
     "g4r_greedy_advance_f32": [P, c_int, P, P, P, P, c_int, P],
     "g4r_sample_advance_f32": [P, c_int, c_float, c_int, c_float, P, P, P, P, P, c_int, P, P],
+    "g4r_sample_rows_f32": [P, c_long, c_int, c_int, P, P, P, P, P, P, P, c_int, P],
     "g4r_swiglu_bf16": [P, P, c_int, c_int, P],
     "g4r_splice_embed_bf16": [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_long, c_long, c_long,
                               c_long, c_int, P],
@@ -975,6 +976,29 @@ def sample_advance(logits_row, tok, out_ids, step, pos, seed, temperature=1.0, t
     _launch("g4r_sample_advance_f32", (_p(logits_row), logits_row.numel(), float(temperature), int(top_k or 0),
                                        float(top_p), _p(seed), _p(tok), _p(out_ids), _p(step), _p(pos),
                                        out_ids.numel(), _p(u_out), _stream(logits_row),))
+
+
+def sample_rows(logits, temperature, top_k, top_p, seed, step, out=None, u_out=None):
+    """One draw per logits row in one launch (include/g4r_kernels.h: g4r_sample_rows_f32): out[b] ~ row b warped by its own
+    temperature[b] / top_k[b] / top_p[b] (fp32 / int32 / fp32 [B]) with the Philox uniform of (step[0], seed[b]) (int64 [B]);
+    temperature[b] <= 0: the argmax of row b (argmax_rows).  u_out [B, cap] fp32 (optional) records u_out[b, step[0]].
+    step is only read: advance the counters with batch_advance(out, ...)."""
+    _f32(logits, temperature, top_p, u_out)
+    _lib.require_gpu(top_k, seed, step)
+    B, N = logits.shape
+    assert logits.stride(1) == 1 and logits.stride(0) >= N
+    assert top_k.dtype == torch.int32 and seed.dtype == torch.int64 and step.dtype == torch.int32
+    for t in (temperature, top_k, top_p, seed):
+        assert t.numel() == B and t.is_contiguous()
+    if out is None:
+        out = torch.empty((B,), dtype=torch.int64, device=logits.device)
+    assert out.dtype == torch.int64 and out.numel() == B and out.is_contiguous()
+    if u_out is not None:
+        assert u_out.dim() == 2 and u_out.size(0) == B and u_out.is_contiguous()
+    _launch("g4r_sample_rows_f32", (_p(logits), logits.stride(0), B, N, _p(temperature), _p(top_k), _p(top_p), _p(seed),
+                                    _p(step), _p(out), _p(u_out), u_out.size(1) if u_out is not None else 0,
+                                    _stream(logits),), tag="sample_rows")
+    return out
 
 
 def argmax_rows(logits):

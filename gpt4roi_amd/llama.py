@@ -119,8 +119,11 @@ class LlamaDecoder:
 
     def _alloc_cache(self, batch):
         L = len(self.layers)
-        self.kc = torch.zeros((L, batch, self.max_positions, self.hidden), dtype=self.dtype, device=self.device)
-        self.vc = torch.zeros_like(self.kc)
+        # a batch larger than the cache may first arrive under inference_mode (ConversationBot.run_batch, app.py:285): the
+        # cache outlives that call, so it stays an ordinary tensor that later calls outside the mode may update in place
+        with torch.inference_mode(False):
+            self.kc = torch.zeros((L, batch, self.max_positions, self.hidden), dtype=self.dtype, device=self.device)
+            self.vc = torch.zeros_like(self.kc)
         self.pos = 0
         self.ragged = None             # RaggedLayout of the prompt in the cache (pad rows squeezed out), or None
         self._dstate = None            # a captured decode graph points into the old cache
@@ -625,18 +628,45 @@ class LlamaDecoder:
             f = norm_proj(x, L['n2'], L['wgu'], h=h2, act="swiglu")
             x, h = proj_res_norm(f, L['wd'], x, self.layers[li + 1]['n1'] if li + 1 < nl else self.norm)
         logits = norm_proj(x, self.norm, self.lm_head, h=h, out_dtype=torch.float32)
-        K.batch_advance(K.argmax_rows(logits), st["tok"], st["tok32"], st["out"], st["step"], st["pos"])
+        self._advance_batch(logits, st)
+
+    @staticmethod
+    def _advance_batch(logits, st):
+        """Token selection of a batched step: the per-row argmax, or -- in a sampled state -- one draw per row with that
+        row's parameters and seed (greedy rows: the same argmax); then the shared counters advance."""
+        if st.get("sampled"):
+            nxt = K.sample_rows(logits, st["temp"], st["topk"], st["topp"], st["seed"], st["step"], u_out=st["u"])
+        else:
+            nxt = K.argmax_rows(logits)
+        K.batch_advance(nxt, st["tok"], st["tok32"], st["out"], st["step"], st["pos"])
 
     @torch.no_grad()
-    def decode_graph_batch(self, inputs_embeds, max_new_tokens, stop_ids=(), use_graph=True, key_padding_mask=None):
-        """generate(do_sample=False) for B sequences, per-token loop on the device.  Prompts of equal length, or -- with
+    def decode_graph_batch(self, inputs_embeds, max_new_tokens, stop_ids=(), use_graph=True, key_padding_mask=None,
+                           sampler=None, seeds=None, on_tokens=None, check_every=None):
+        """generate() for B sequences, per-token loop on the device.  Prompts of equal length, or -- with
         key_padding_mask (bool [B, T]) -- prompts padded to a common T on either side (HF batch generation pads on the
         left; merged serving requests of different lengths pad on the right): see `forward`.  Prefill
         eagerly, then one captured hipGraph replay per step for the whole batch (token ids, position and output slots stay
         in device memory).  The 13.2 GB weight stream of a step is shared by the B sequences -- the throughput mode of
-        SURVEY.md 8d config 5.  Sequences that hit a stop id keep running; their later tokens are cut from the result.
-        Returns a list of B id lists (same ids as greedy_batch, the host-loop form)."""
+        SURVEY.md 8d config 5.  Returns a list of B id lists (greedy: the same ids as greedy_batch, the host-loop form).
+
+        sampler: None (greedy), one (temperature, top_k, top_p) for every row, or a list of B entries, each None (greedy
+        row) or a tuple -- one g4r_sample_rows_f32 launch draws every row with its own parameters, which live in device
+        memory with the seeds (one captured graph per (B, ragged) serves any mix).  seeds: None (drawn from torch's
+        generator), an int s (row b: (s + b * 0x9E3779B97F4A7C15) mod 2^64, so row 0 draws the stream of
+        decode_graph(seed=s)) or a list of B ints.  The uniforms are recorded in the batch state (`u` [B, cap]).
+
+        Stopping.  Greedy without on_tokens: every row runs max_new_tokens steps and is cut after its first stop id.
+        Sampled, or with on_tokens(b, ids of row b so far) -> bool: every `check_every` steps (default 32) the host reads
+        the new ids; row b is finished at its first stop id or the first prefix on_tokens accepts (each prefix is shown
+        once), the loop ends when every row has finished, and each row is cut at its own end (inclusive); self.pos then
+        counts the steps actually run."""
+        from .generation import expand_seeds, row_samplers
         B = inputs_embeds.size(0)
+        rows = row_samplers(sampler, B)
+        sampled = any(r is not None for r in rows)
+        early = sampled or on_tokens is not None
+        every = max(1, int(check_every)) if check_every is not None else 32
         self.reset(B)
         logits = self.forward(inputs_embeds, all_logits=False, key_padding_mask=key_padding_mask)
         T = self.pos
@@ -646,45 +676,83 @@ class LlamaDecoder:
         pool = getattr(self, "_bstate", None)
         if pool is None:
             pool = self._bstate = {}
-        bs = pool.get((B, ragged))
+        key = (B, ragged, True) if sampled else (B, ragged)             # the greedy state keeps its key and its graph
+        bs = pool.get(key)
         if bs is None or bs["out"].size(1) < max_new_tokens:
             cap = max(64, 1 << (max_new_tokens - 1).bit_length())      # output slots: the captured graph knows this stride
             with torch.inference_mode(False):
-                bs = pool[(B, ragged)] = dict(B=B, ragged=ragged, tok=torch.zeros(B, dtype=torch.int64, device=dev),
-                                              tok32=torch.zeros(B, dtype=torch.int32, device=dev),
-                                              out=torch.zeros((B, cap), dtype=torch.int64, device=dev),
-                                              pos=torch.zeros(B + 1 if ragged else 1, dtype=torch.int32, device=dev),
-                                              step=torch.zeros(1, dtype=torch.int32, device=dev), graph=None)
+                bs = pool[key] = dict(B=B, ragged=ragged, tok=torch.zeros(B, dtype=torch.int64, device=dev),
+                                      tok32=torch.zeros(B, dtype=torch.int32, device=dev),
+                                      out=torch.zeros((B, cap), dtype=torch.int64, device=dev),
+                                      pos=torch.zeros(B + 1 if ragged else 1, dtype=torch.int32, device=dev),
+                                      step=torch.zeros(1, dtype=torch.int32, device=dev), graph=None)
+                if sampled:
+                    bs.update(sampled=True, temp=torch.zeros(B, dtype=torch.float32, device=dev),
+                              topk=torch.zeros(B, dtype=torch.int32, device=dev),
+                              topp=torch.ones(B, dtype=torch.float32, device=dev),
+                              seed=torch.zeros(B, dtype=torch.int64, device=dev),
+                              u=torch.zeros((B, cap), dtype=torch.float32, device=dev))
         st = bs
+        if sampled:
+            seeds = expand_seeds(seeds, B)
+            st["temp"].copy_(torch.tensor([r[0] if r else 0.0 for r in rows], dtype=torch.float32))
+            st["topk"].copy_(torch.tensor([int(r[1]) if r else 0 for r in rows], dtype=torch.int32))
+            st["topp"].copy_(torch.tensor([r[2] if r else 1.0 for r in rows], dtype=torch.float32))
+            st["seed"].copy_(torch.tensor([x - 2 ** 64 if x >= 2 ** 63 else x for x in seeds], dtype=torch.int64))
+            st["u"].zero_()
         if ragged:
             st["pos"].copy_(self._rag_pos - 1)                          # [n_b - 1 ..., T - 1]: the advance below moves them on
         else:
             st["pos"].fill_(T - 1)
         st["step"].zero_()
-        K.batch_advance(K.argmax_rows(logits.view(B, -1)), st["tok"], st["tok32"], st["out"], st["step"], st["pos"])
+        self._advance_batch(logits.view(B, -1), st)
         done = 1
-        if max_new_tokens > 1:
+        ends, checked = [None] * B, [0] * B         # per row: its length once finished; the prefixes already looked at
+
+        def finished(n):
+            ids = st["out"][:, :n].tolist()
+            for b in range(B):
+                if ends[b] is not None:
+                    continue
+                for m in range(checked[b] + 1, n + 1):     # each prefix once, token by token
+                    if ids[b][m - 1] in stop_ids or (on_tokens is not None and on_tokens(b, ids[b][:m])):
+                        ends[b] = m
+                        break
+                else:
+                    checked[b] = n
+            return all(e is not None for e in ends)
+
+        all_done = finished(done) if early else False
+        if not all_done and max_new_tokens > 1:
             self._decode_step_batch(st)                                  # token 2 (also warms up)
             done = 2
-        if use_graph and st["graph"] is None and max_new_tokens > 2:
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.inference_mode(False), torch.no_grad():
-                with torch.cuda.graph(g):                                # (recorded, not executed: the state does not move)
+            if use_graph and st["graph"] is None and max_new_tokens > 2:
+                torch.cuda.synchronize()
+                g = torch.cuda.CUDAGraph()
+                with torch.inference_mode(False), torch.no_grad():
+                    with torch.cuda.graph(g):                            # (recorded, not executed: the state does not move)
+                        self._decode_step_batch(st)
+                st["graph"] = g
+        while not all_done and done < max_new_tokens:
+            n = min(every, max_new_tokens - done) if early else max_new_tokens - done
+            for _ in range(n):
+                if st["graph"] is not None:
+                    st["graph"].replay()
+                else:
                     self._decode_step_batch(st)
-            st["graph"] = g
-        while done < max_new_tokens:
-            if st["graph"] is not None:
-                st["graph"].replay()
-            else:
-                self._decode_step_batch(st)
-            done += 1
-        self.pos = T + max_new_tokens - 1
-        res = []
-        for row in st["out"][:, :max_new_tokens].tolist():
-            hit = [i for i, t in enumerate(row) if t in stop_ids]
-            res.append(row[:hit[0] + 1] if hit else row)
-        return res
+            done += n
+            if early:
+                all_done = finished(done)
+        if not early:
+            self.pos = T + max_new_tokens - 1
+            res = []
+            for row in st["out"][:, :max_new_tokens].tolist():
+                hit = [i for i, t in enumerate(row) if t in stop_ids]
+                res.append(row[:hit[0] + 1] if hit else row)
+            return res
+        self.pos = T + done - 1                                          # the last token was not fed back
+        out = st["out"][:, :done].tolist()
+        return [row[:ends[b]] if ends[b] is not None else row for b, row in enumerate(out)]
 
     @torch.no_grad()
     def greedy_batch(self, inputs_embeds, max_new_tokens, stop_ids=(), key_padding_mask=None):

@@ -10,6 +10,7 @@ Mirrors gpt4roi/app.py:
                                         region lose their brackets
   ConversationBot.run         :243-328  KeywordsStoppingCriteria('###'), forward bound with partial(bboxes=...), sampling
                                         generate(temperature 0.2, <= 1024 new tokens), answer clean-up, history update
+  ConversationBot.run_batch             the same round for several conversations in one left-padded batched generate()
 Not mirrored: Gradio widgets, the box overlay drawing (`visualize`), chat-history HTML escaping.
 
 The history cache has the reference's structure (a list whose last entry holds 'sources', 'region_name_set', 'bboxes') and
@@ -162,7 +163,11 @@ class ConversationBot:
             finally:
                 model.forward = model.orig_forward
         T = input_ids.shape[1]
-        answer = self.tokenizer.batch_decode(output_ids[:, T:], skip_special_tokens=True)[0].strip()
+        return self._answer(output_ids[:, T:], history_cache)
+
+    def _answer(self, new_ids, history_cache):
+        """New ids [1, n] -> (answer shown, None, history_cache): the clean-up and history update of app.py:309-328."""
+        answer = self.tokenizer.batch_decode(new_ids, skip_special_tokens=True)[0].strip()
         if answer.endswith(STOP_STR):
             answer = answer[:-len(STOP_STR)]
         answer = answer.strip() or EMPTY_ANSWER
@@ -170,3 +175,73 @@ class ConversationBot:
         answer = answer.replace('Assistant: ', '').replace('Assistant:', '')
         history_cache[-1]['sources']['conversations'].append({'from': 'gpt', 'value': answer})
         return shown, None, history_cache
+
+    def batch_inputs(self, texts, images, history_caches):
+        """check_input + init_inputs for each conversation, then the batch: prompts LEFT-padded with the tokenizer's pad id
+        (HF batch generation style) -> (results, rows, dict(input_ids [B, T], attention_mask [B, T], images [B, 3, S, S],
+        bboxes list of B)).  results[i] is (None, error, history_caches[i]) for a conversation that fails its check, else
+        None; rows lists the conversations in the batch, in order."""
+        results, rows, ids, imgs, boxes = [None] * len(texts), [], [], [], []
+        for i, (text, image, hist) in enumerate(zip(texts, images, history_caches)):
+            error, text = self.check_input(text, image, hist)
+            if error is not None:
+                results[i] = (None, error, hist)
+                continue
+            text = text.strip() or 'hello, world!'           # app.py:256-258
+            inputs, history_caches[i] = self.init_inputs(image, text, hist)
+            rows.append(i)
+            ids.append(inputs['input_ids'])
+            imgs.append(inputs['image'])
+            bb = inputs['bboxes']
+            boxes.append(bb.to(self.device) if bb is not None else torch.zeros(0, 4, device=self.device))
+        if not rows:
+            return results, rows, None
+        T = max(int(x.numel()) for x in ids)
+        pad = self.tokenizer.pad_token_id
+        input_ids = torch.full((len(rows), T), pad, dtype=torch.int64)
+        mask = torch.zeros((len(rows), T), dtype=torch.int64)
+        for r, x in enumerate(ids):
+            input_ids[r, T - x.numel():] = x
+            mask[r, T - x.numel():] = 1
+        batch = dict(input_ids=input_ids.to(self.device), attention_mask=mask.to(self.device),
+                     images=torch.stack([im.to(self.device) for im in imgs], 0), bboxes=boxes)
+        return results, rows, batch
+
+    def run_batch(self, texts, images, history_caches, do_sample=True, temperature=0.2, max_new_tokens=1024, seeds=None):
+        """Several conversations, one question each, answered by ONE batched generate(): -> list of
+        (answer or None, error or None, history_cache), one per conversation.  Each conversation is checked and assembled
+        as `run` does it; those that fail the check return their error and stay out of the batch.  The prompts are
+        left-padded into one batch that decodes together (the weight stream of a step is shared), each sequence sampled
+        with its own Philox stream and stopped by the '###' criterion on its own ids; the answers are cleaned up and
+        appended to each history exactly as `run` does.  seeds: None (drawn), an int (expanded over the batch rows, see
+        generate) or a list with one seed per conversation (a conversation then draws what `run(seed=...)` would draw on
+        the same logits).  `run` stays the batch-1 path."""
+        results, rows, batch = self.batch_inputs(texts, images, history_caches)
+        if not rows:
+            return results
+        if isinstance(seeds, (list, tuple)):
+            if len(seeds) != len(texts):
+                raise ValueError(f"{len(seeds)} seeds for {len(texts)} conversations")
+            seeds = [seeds[i] for i in rows]
+        input_ids = batch['input_ids']
+        T = input_ids.size(1)
+        # one '###' criterion for the batch: built on the padded prompts (T = its start length), generate() applies it to
+        # every row on that row's own ids, so it acts for each conversation as run()'s criterion does for one
+        criteria = KeywordsStoppingCriteria([STOP_STR], self.tokenizer, input_ids)
+        model = self.model
+        with torch.inference_mode():
+            model.orig_forward = model.forward
+            model.forward = partial(model.orig_forward, img_metas=[None] * len(rows), bboxes=batch['bboxes'])
+            try:
+                new = model.generate(input_ids, images=batch['images'], attention_mask=batch['attention_mask'],
+                                     do_sample=do_sample, temperature=temperature, max_new_tokens=max_new_tokens,
+                                     stopping_criteria=[criteria], seed=seeds, pad_token_id=self.tokenizer.pad_token_id,
+                                     return_new_tokens=True)
+            finally:
+                model.forward = model.orig_forward
+        if len(rows) == 1:
+            new = [new]
+        for r, i in enumerate(rows):
+            ids = torch.tensor([new[r]], dtype=torch.int64).reshape(1, -1)
+            results[i] = self._answer(ids, history_caches[i])
+        return results

@@ -39,7 +39,7 @@ import torch.nn as nn
 
 from . import kernels as K
 from .generation import (KeywordsStoppingCriteria, SamplingConfig, StoppingCriteria,  # noqa: F401 (re-exported)
-                         dense_or_mask, prepare_inputs_for_generation)
+                         dense_or_mask, expand_seeds, prepare_inputs_for_generation)
 from .layers import MLVLROIQueryModule, PreparedBoxes
 from .llama import LlamaDecoder
 from .vit import ClipVisionTower
@@ -619,12 +619,25 @@ class SPILlavaMPTForCausalLM(nn.Module):
         (drawn from torch's generator when None).  `stopping_criteria`: callables criteria(ids [1, T+n], scores) -> bool
         evaluated per generated token like HF (KeywordsStoppingCriteria); `eos_token_id` / `stop_ids` end the sequence
         (inclusive).  Returns the full sequence LongTensor [1, T + n] (or the list of new ids if return_new_tokens).
-        Batch B > 1 (greedy only): prompts padded to one length with `attention_mask` marking the real tokens (left padding
-        as HF batch generation uses it, or right padding) decode together, every sequence continuing from its own length
-        with the positions of the padded layout (LlamaDecoder.forward); rows that stopped are filled with pad_token_id."""
+        Batch B > 1: prompts padded to one length with `attention_mask` marking the real tokens (left padding as HF batch
+        generation uses it, or right padding) decode together, every sequence continuing from its own length with the
+        positions of the padded layout (LlamaDecoder.forward); rows that stopped are filled with pad_token_id.  Sampling
+        takes the same do_sample / temperature / top_k / top_p for every row, one draw per row per step on the device
+        (g4r_sample_rows_f32); `seed` is an int (row b keys its stream with (seed + b * 0x9E3779B97F4A7C15) mod 2^64, so
+        row 0 draws what a batch-1 call with that seed draws) or a list of B ints (each row as if served alone with its
+        seed).  `stopping_criteria` are applied PER SEQUENCE, unlike HF's whole-batch criteria: every criterion is called
+        once with the prompt (row 0, [1, T]: KeywordsStoppingCriteria records its start length there), then with each
+        row's own [1, T + n] ids (padded prompt + that row's new ids); a row stops at the first token for which any
+        criterion returns true, and the decode ends when every row has stopped -- a request merged into a batch behaves
+        as if it were served alone."""
         if input_ids.size(0) > 1:
-            return self._generate_batch(input_ids, images, max_new_tokens, do_sample, stopping_criteria, eos_token_id,
-                                        bboxes, stop_ids, return_new_tokens, attention_mask, pad_token_id)
+            return self._generate_batch(input_ids, images, max_new_tokens, do_sample, temperature, top_k, top_p, seed,
+                                        stopping_criteria, eos_token_id, bboxes, stop_ids, check_every, return_new_tokens,
+                                        attention_mask, pad_token_id)
+        if isinstance(seed, (list, tuple)):
+            if len(seed) != 1:
+                raise ValueError(f"{len(seed)} seeds for a batch of 1 sequence")
+            seed = seed[0]
         gc = self.generation_config
         cfg = SamplingConfig(do_sample=gc.do_sample if do_sample is None else bool(do_sample),
                              temperature=gc.temperature if temperature is None else temperature,
@@ -662,10 +675,16 @@ class SPILlavaMPTForCausalLM(nn.Module):
             return new
         return torch.cat([input_ids, torch.tensor([new], dtype=input_ids.dtype, device=input_ids.device)], 1)
 
-    def _generate_batch(self, input_ids, images, max_new_tokens, do_sample, stopping_criteria, eos_token_id, bboxes,
-                        stop_ids, return_new_tokens, attention_mask, pad_token_id):
-        if (self.generation_config.do_sample if do_sample is None else do_sample) or stopping_criteria:
-            raise NotImplementedError("batched generate() is greedy and stops on ids (sampling / criteria: one request at a time)")
+    def _generate_batch(self, input_ids, images, max_new_tokens, do_sample, temperature, top_k, top_p, seed,
+                        stopping_criteria, eos_token_id, bboxes, stop_ids, check_every, return_new_tokens, attention_mask,
+                        pad_token_id):
+        B = input_ids.size(0)
+        gc = self.generation_config
+        cfg = SamplingConfig(do_sample=gc.do_sample if do_sample is None else bool(do_sample),
+                             temperature=gc.temperature if temperature is None else temperature,
+                             top_k=gc.top_k if top_k is None else top_k, top_p=gc.top_p if top_p is None else top_p)
+        sampler = cfg.sampler()
+        seeds = expand_seeds(seed, B) if sampler is not None else None      # (validates a list's length before any work)
         kw = dict(bboxes=bboxes) if bboxes is not None else {}
         embeds = self._prefill_embeds(self.forward, self.prepare_inputs_for_generation(input_ids, images=images), kw)
         stops = set(int(s) for s in stop_ids)
@@ -673,7 +692,18 @@ class SPILlavaMPTForCausalLM(nn.Module):
             eos_token_id = getattr(self.config, "eos_token_id", None)
         if eos_token_id is not None:
             stops.update([int(eos_token_id)] if not isinstance(eos_token_id, (list, tuple)) else map(int, eos_token_id))
-        new = self.model.llama.decode_graph_batch(embeds, max_new_tokens, stop_ids=stops, key_padding_mask=attention_mask)
+        on_tokens = None
+        if stopping_criteria:
+            for c in stopping_criteria:                      # the arming call of the batch-1 path, with a [1, T] prompt
+                c(input_ids[:1], None)
+
+            def on_tokens(b, new_ids):                       # row b alone: its padded prompt + its own new ids
+                row = input_ids[b:b + 1]
+                seq = torch.cat([row, torch.tensor([new_ids], dtype=row.dtype, device=row.device)], 1)
+                return any(bool(c(seq, None)) for c in stopping_criteria)
+        every = check_every if check_every is not None else (1 if stopping_criteria else 32)
+        new = self.model.llama.decode_graph_batch(embeds, max_new_tokens, stop_ids=stops, key_padding_mask=attention_mask,
+                                                  sampler=sampler, seeds=seeds, on_tokens=on_tokens, check_every=every)
         if return_new_tokens:
             return new
         pad = pad_token_id if pad_token_id is not None else (getattr(self.config, "pad_token_id", None) or 0)

@@ -292,6 +292,19 @@ int g4r_sample_advance_f32(const float* logits, int N, float temperature, int to
                            const unsigned long long* seed, long* tok, long* out_ids, int* step, int* pos,
                            int max_steps, float* u_out, void* stream);
 
+/*
+ * Batched sampling step (generate(do_sample=True) for B sequences decoded together): one 1024-thread workgroup per logits
+ * row, each with its own temperature[b], top_k[b], top_p[b], seed[b] read from device memory (one captured hipGraph serves
+ * any mix of settings and seeds).  Row b draws exactly as g4r_sample_advance_f32 would with the same seed, using
+ * u = Philox4x32-10(counter = (*step, 0, 0, 0), key = seed[b])[0] >> 8 scaled to [0, 1); temperature[b] <= 0 makes row b
+ * greedy (the id g4r_argmax_rows_f32 returns, lowest index on ties).  next_ids[b] = id; u_out[b * u_stride + *step] = u
+ * (nullable; written while *step < u_stride).  *step is only read: g4r_batch_advance / g4r_batch_advance_ragged move the
+ * counters afterwards.  top_k in [0, 1024]; top_p < 1 needs top_k >= 1 (the caller validates: the values live on the device).
+ */
+int g4r_sample_rows_f32(const float* logits, long row_stride, int B, int N, const float* temperature, const int* top_k,
+                        const float* top_p, const unsigned long long* seed, const int* step, long* next_ids, float* u_out,
+                        int u_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
