@@ -6,6 +6,7 @@ here with torch.empty (PyTorch is only the allocator / stream provider).
 """
 import ctypes
 import os
+from collections import namedtuple
 from ctypes import c_float, c_int, c_long, c_void_p
 
 import torch
@@ -324,27 +325,75 @@ def wave_split(M, N, K):
     return n_main
 
 
-def long_k_plan(M, N, K):
-    """(tile_cfg, K slices) for the long-K / few-tiles shape of the LLaMA down_proj (767 x 4096 x 11008: 48 tiles of 256 x 256),
-    or None: the 192 x 256 ring ping-pong tile x 4 K-slices = 64 x 4 = 256 workgroups."""
-    if K >= 8192 and K % 64 == 0 and (-(-M // 256) * 256) <= 1.1 * M and 32 <= -(-M // 256) * -(-N // 256) <= 64:
-        # round 5: 48 tiles of 256 x 256 x 4 K slices on the one-wave-per-SIMD tile 78.3 us vs 83.9 (profiles/r05_m767_sweep.txt)
-        return (34, 4) if BIG_TILE == 34 else (28, 4)
-    return None
+# One launch of gemm(): weight rows (= output columns) [n0, n1) on `kernel` -- "gemv_batch" (g4r_gemv_batch_bf16) or "tile"
+# (g4r_gemm_bf16_nt with tile id `tile` and `splits` K slices); `rule` names the rule of gemm_plan that chose it.
+Launch = namedtuple("Launch", "kernel n0 n1 tile splits rule")
 
 
-def partial_wave_plan(M, N, K):
-    """(tile_cfg, K slices) for a long-K shape that covers a quarter to a half of one wave of 256 x 256 tiles -- the column
-    remainder `wave_split` leaves behind in the training batch (5592 x 1280 x {11008, 12288, 22016}: 110 tiles) -- or None.
-    K slices on the ring ping-pong kernel until tiles x slices fills the 256 CUs: 153 vs 186 us at K = 11008, 169 vs 215 at
-    12288, 300 vs 377 at 22016 against the two-stage 128 x 128 tile (profiles/r03_gemm_partial_wave.txt).  Not for K = 4096
-    (equal) and not for fp32 outputs (lm_head remainder: 118 vs 91 us -- the fp32 partials cost more than the wave gains)."""
-    if not (K >= 8192 and K % 64 == 0 and (-(-M // 256) * 256) <= 1.1 * M):
-        return None
-    t256 = -(-M // 256) * -(-N // 256)
-    if 64 < t256 <= 128:
-        return BIG_TILE, 256 // t256
-    return None
+def gemm_plan(M, N, K, *, fp32_out=False, gemv_ok=True, n0=0):
+    """THE routing decision of a[M,K] @ w[N,K]^T: every launch gemm() issues when its caller names no tile, K slices or
+    workspace, as a list of Launch in issue order (gemm() executes it; the *_plan queries below read it).  Pure: sizes in, no
+    tensors.  fp32_out: the output is fp32; gemv_ok: the weight-streaming kernel can read the operands (gemv_batch_ok); n0: the
+    first column (the planner's own recursion).  BIG_TILE and the GEMV_BATCH_* knobs are read per call: tools set them."""
+    if gemv_ok and gemv_batch_wins(M, N, K):
+        # a handful of rows (the decode step of a batch of sequences): weight streaming with the products on the matrix pipe
+        return [Launch("gemv_batch", n0, n0 + N, 0, 1, "gemv_batch")]
+    tile = pick_tile(M, N, K)
+    mt = -(-M // 256)
+    t256 = mt * -(-N // 256)
+    # several whole waves of 256 x 256 tiles plus a THIN last one (batch-4 gate|up 3068 x 22016: 1032 tiles = 4 waves + 8
+    # tiles): the last columns go to a second launch as K slices instead of costing a fifth wave
+    thin_tail = M >= 1024 and tile == BIG_TILE and not fp32_out and t256 > 256 and 0 < t256 % 256 <= 48
+    if tile not in (24, 28, 34) or thin_tail:
+        n_main = wave_split(M, N, K)
+        if n_main is not None:
+            main = Launch("tile", n0, n0 + n_main, BIG_TILE, 1, "wave_split")
+            rem_tiles = mt * -(-(N - n_main) // 256)
+            if thin_tail and rem_tiles <= 64:
+                return [main, Launch("tile", n0 + n_main, n0 + N, BIG_TILE, max(2, min(16, 256 // rem_tiles, K // 256)), "thin_tail")]
+            # (the remainder is a small GEMM of its own; it has too many rows for the weight-streaming kernel)
+            return [main] + gemm_plan(M, N - n_main, K, fp32_out=fp32_out, gemv_ok=False, n0=n0 + n_main)
+    if K >= 8192 and K % 64 == 0 and mt * 256 <= 1.1 * M:
+        if 32 <= t256 <= 64:
+            # the long-K / few-tiles shape of the LLaMA down_proj (767 x 4096 x 11008: 48 tiles of 256 x 256).  Round 3: the 192x256
+            # ring ping-pong tile x 4 K-slices (64 x 4 = 256 workgroups) 85.0 us vs 88.0 (256x256 x 5) and 87.6 (one wave per
+            # SIMD x 5), reduce included, and 115.3 for the 128x128 ring (tools/gemm_bench.cpp, profiles/r02_gemm_tiles.md)
+            # round 5: 48 tiles of 256 x 256 x 4 K slices on the one-wave-per-SIMD tile 78.3 us vs 83.9 (profiles/r05_m767_sweep.txt)
+            return [Launch("tile", n0, n0 + N, 34 if BIG_TILE == 34 else 28, 4, "long_k")]
+        if 64 < t256 <= 128 and not fp32_out:
+            # a quarter to a half of one wave of 256 x 256 tiles -- the column remainder `wave_split` leaves behind in the
+            # training batch (5592 x 1280 x {11008, 12288, 22016}: 110 tiles).  K slices on the ring ping-pong kernel until
+            # tiles x slices fills the 256 CUs: 153 vs 186 us at K = 11008, 169 vs 215 at 12288, 300 vs 377 at 22016 against the
+            # two-stage 128 x 128 tile (profiles/r03_gemm_partial_wave.txt).  Not for K = 4096 (equal) and not for fp32 outputs
+            # (lm_head remainder: 118 vs 91 us -- the fp32 partials cost more than the wave gains)
+            return [Launch("tile", n0, n0 + N, BIG_TILE, 256 // t256, "partial_wave")]
+    splits = 1
+    if tile == 14 and K >= 4096:
+        t64 = -(-M // 64) * -(-N // 64)
+        if t64 <= 64:
+            splits = 4                 # <= 64 tiles: the gate|up remainder 767x256x4096 13.8 vs 17.2 us (x2) / 23.6 (x1);
+            #                            batched decode o_proj / down_proj 8x4096x4096 13.4 vs 23.6, x11008 24.9 vs 54.8
+        elif t64 <= 256 and M > 64:
+            splits = 2                 # ViT fc2 577x1024x4096: 24.2 us vs 27.1 unsplit (29.4 before: 64x128 x 3 splits)
+        #                                (M <= 64 = batched decode, wide projections: measured unsplit, 25.4 / 40.1 us)
+    return [Launch("tile", n0, n0 + N, tile, splits, "pick_tile" if splits == 1 else "small_m" if M > 64 else "decode")]
+
+
+def _sliced_by(rule):
+    """-> query(M, N, K) = (tile_cfg, K slices) when gemm() runs a 16-bit [M,K] x [N,K] problem as ONE launch of K slices chosen
+    by `rule`, else None.  A caller may then issue gemm_partials itself and fold the reduce into the norm that follows
+    (rmsnorm_splitk / layernorm_splitk: the same slices, the same sums).  Each caller takes the one rule it was measured with."""
+    def query(M, N, K):
+        plan = gemm_plan(M, N, K)
+        return (plan[0].tile, plan[0].splits) if len(plan) == 1 and plan[0].rule == rule and plan[0].splits > 1 else None
+    return query
+
+
+# LlamaDecoder.forward, down_proj of one prefill (767 x 4096 x 11008) -- not the "partial_wave" slices of two merged requests
+long_k_plan = _sliced_by("long_k")
+small_m_split_plan = _sliced_by("small_m")        # ClipVisionTower.forward: fc2 at batch 1 (577 x 1024 x 4096)
+decode_split_plan = _sliced_by("decode")          # LlamaDecoder._decode_step_batch: o_proj / down_proj (8 x 4096 x {4096, 11008})
+partial_wave_plan = _sliced_by("partial_wave")    # (no caller fuses this one; tests pin it)
 
 
 def gemm_partials(a, w, splits, tile_cfg):
@@ -375,24 +424,6 @@ def rmsnorm_splitk(partials, n_slices, residual, gamma, eps=1e-6):
                                         _p(x), x.stride(0), _p(gamma), _p(y), y.stride(0), M, N, float(eps), _stream(x),),
             tag="g4r_rmsnorm_bf16", dt=dt)
     return x, y
-
-
-def small_m_split_plan(M, N, K):
-    """(tile_cfg, K slices) when gemm() would run this shape as K slices on the 64x64 ring tile (CLIP fc2 at batch 1:
-    577 x 1024 x 4096), or None."""
-    if pick_tile(M, N, K) == 14 and K >= 4096 and -(-M // 64) * -(-N // 64) <= 256 and M > 64:
-        return 14, (4 if -(-M // 64) * -(-N // 64) <= 64 else 2)
-    return None
-
-
-def decode_split_plan(M, N, K):
-    """(tile_cfg, K slices) when gemm() runs a batched-decode projection (a handful of rows) as K slices on the 64x64 ring tile
-    followed by a reduce launch -- o_proj / down_proj of LlamaDecoder._decode_step_batch: 8 x 4096 x {4096, 11008} -- or None.
-    The step then hands the partials to rmsnorm_splitk (reduce + residual + the next RMSNorm in one launch, same bits)."""
-    if 1 < M <= 64 and not gemv_batch_wins(M, N, K) and pick_tile(M, N, K) == 14 and K >= 4096 and K % 64 == 0 \
-            and -(-M // 64) * -(-N // 64) <= 64:
-        return 14, 4                                     # (the branch of gemm() with the same conditions)
-    return None
 
 
 def layernorm_splitk(partials, n_slices, bias, residual, gamma, beta, eps=1e-5):
@@ -451,65 +482,33 @@ def gemm(a, w, bias=None, residual=None, act=None, out=None, out_dtype=None, spl
     assert out.dtype in (dt, torch.float32), f"gemm: out is {out.dtype}, operands are {dt}"     # (the epilogue writes dt or fp32 bits)
     if residual is not None:
         assert residual.shape == (M, N) and residual.stride(1) == 1
-    if tile_cfg is None and splits == 1 and workspace is None and gemv_batch_wins(M, N, K) and a.stride(0) % 8 == 0 \
-            and a.stride(0) >= K and w.stride(0) % 8 == 0 and (residual is None or residual.data_ptr() != out.data_ptr()) \
-            and a.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0:        # (the kernel reads both operands in 16-byte pieces)
-        # a handful of rows (the decode step of a batch of sequences): weight streaming with the products on the matrix pipe
-        return gemv_batch(a, w, bias=bias, residual=residual, act=act, out=out, variant=GEMV_BATCH_VARIANT)
-    thin_tail = False
-    if tile_cfg is None and splits == 1 and M >= 1024 and pick_tile(M, N, K) == BIG_TILE and out.dtype != torch.float32:
-        # several whole waves of 256 x 256 tiles plus a THIN last one (batch-4 gate|up 3068 x 22016: 1032 tiles = 4 waves + 8
-        # tiles): the last columns go to a second launch as K slices instead of costing a fifth wave
-        t256 = -(-M // 256) * -(-N // 256)
-        thin_tail = t256 > 256 and 0 < t256 % 256 <= 48
-    if tile_cfg is None and splits == 1 and (pick_tile(M, N, K) not in (24, 28, 34) or thin_tail):
-        n_main = wave_split(M, N, K)
-        if n_main is not None:
-            o_main = n_main // 2 if act == "swiglu" else n_main
-            gemm(a, w[:n_main], bias[:n_main] if bias is not None else None,
-                 residual[:, :n_main] if residual is not None else None, act, out[:, :o_main], tile_cfg=BIG_TILE)
-            rem_tiles = -(-M // 256) * -(-(N - n_main) // 256)
-            if thin_tail and rem_tiles <= 64:
-                gemm(a, w[n_main:], bias[n_main:] if bias is not None else None,
-                     residual[:, n_main:] if residual is not None else None, act, out[:, o_main:], tile_cfg=BIG_TILE,
-                     splits=max(2, min(16, 256 // rem_tiles, K // 256)))
-            else:
-                gemm(a, w[n_main:], bias[n_main:] if bias is not None else None,
-                     residual[:, n_main:] if residual is not None else None, act, out[:, o_main:])
-            return out
-    if tile_cfg is None and splits == 1 and long_k_plan(M, N, K) is not None:
-        # LLaMA down_proj 767x4096x11008 (48 tiles of 256x256): 5 K-slices on the one-wave-per-SIMD kernel, 100.2 us
-        # (incl. the reduce) vs 110.4 for the ring ping-pong kernel x 4 slices and 115.3 for the 128x128 ring on the
-        # same box (tools/gemm_bench.cpp, profiles/r02_gemm_tiles.md)
-        # round 3: with the pieces as buffer loads the 192x256 ring ping-pong tile x 4 K-slices (64 x 4 = 256 workgroups) is
-        # the best form: 85.0 us vs 88.0 (256x256 x 5) and 87.6 (one wave per SIMD x 5), reduce included
-        tile_cfg, splits = long_k_plan(M, N, K)
-    if tile_cfg is None and splits == 1 and out.dtype != torch.float32 and partial_wave_plan(M, N, K) is not None:
-        tile_cfg, splits = partial_wave_plan(M, N, K)
-    if tile_cfg is None:
-        tile_cfg = pick_tile(M, N, K)
-        if splits == 1 and tile_cfg == 4 and K >= 2048 and K % 64 == 0 and M > 1:
-            # few tiles and a long K: split K so the grid covers the 256 CUs
-            tiles = -(-M // 64) * -(-N // 128)
-            if tiles < 160:
-                splits = max(1, min(4, 256 // tiles, K // 1024))
-        if splits == 1 and tile_cfg == 14 and K >= 4096 and -(-M // 64) * -(-N // 64) <= 256:
-            splits = 2                 # ViT fc2 577x1024x4096: 24.2 us vs 27.1 unsplit (29.4 before: 64x128 x 3 splits)
-            if -(-M // 64) * -(-N // 64) <= 64:
-                splits = 4             # <= 64 tiles: the gate|up remainder 767x256x4096 13.8 vs 17.2 us (x2) / 23.6 (x1);
-                #                        batched decode o_proj / down_proj 8x4096x4096 13.4 vs 23.6, x11008 24.9 vs 54.8
-            elif M <= 64:
-                splits = 1             # batched decode, wide projections: measured unsplit (25.4 / 40.1 us)
-    if splits > 1 and workspace is None:
-        workspace = torch.empty((splits, M, N), dtype=torch.float32, device=a.device)
-    _launch("g4r_gemm_bf16_nt", (
-        _p(a), _p(w), _p(out), _p(bias), _p(residual), _p(workspace), M, N, K, a.stride(0), w.stride(0),
-        out.stride(0), residual.stride(0) if residual is not None else 0, ACT[act],
-        1 if out.dtype == torch.float32 else 0, splits, tile_cfg, _stream(a),),
-        tag="gemv_bf16" if (M == 1 and splits == 1 and K >= 512 and K % 8 == 0) else
-        ((f"gemm_bf16_nt<{TILE_NAMES.get(tile_cfg, tile_cfg)}>" + ("+splitk" if splits > 1 else "")) if K % 64 == 0
-         else "small_linear") + (f" {M}x{N}x{K}" if PROFILER.detail else ""),
-        flops=2.0 * M * N * K, nbytes=2.0 * (M * K + N * K) + out.element_size() * M * N, dt=dt)
+    if tile_cfg is None and splits == 1:
+        # (a caller's workspace only rules out the weight-streaming kernel, and serves a plan of one launch)
+        plan = gemm_plan(M, N, K, fp32_out=out.dtype == torch.float32,
+                         gemv_ok=workspace is None and gemv_batch_ok(a, w, residual, out))
+    else:
+        plan = [Launch("tile", 0, N, pick_tile(M, N, K) if tile_cfg is None else tile_cfg, splits, "caller")]
+    for kernel, n0, n1, tile, ns, _ in plan:
+        n, w_, b_, r_, o_ = n1 - n0, w, bias, residual, out
+        if n != N:                                   # a column range: swiglu pairs two weight rows per output column
+            half = 2 if act == "swiglu" else 1
+            w_, o_ = w[n0:n1], out[:, n0 // half:n1 // half]
+            b_ = bias[n0:n1] if bias is not None else None
+            r_ = residual[:, n0:n1] if residual is not None else None
+        if kernel == "gemv_batch":
+            gemv_batch(a, w_, bias=b_, residual=r_, act=act, out=o_, variant=GEMV_BATCH_VARIANT)
+            continue
+        ws = workspace if len(plan) == 1 else None
+        if ns > 1 and ws is None:
+            ws = torch.empty((ns, M, n), dtype=torch.float32, device=a.device)
+        _launch("g4r_gemm_bf16_nt", (
+            _p(a), _p(w_), _p(o_), _p(b_), _p(r_), _p(ws), M, n, K, a.stride(0), w_.stride(0),
+            o_.stride(0), r_.stride(0) if r_ is not None else 0, ACT[act],
+            1 if out.dtype == torch.float32 else 0, ns, tile, _stream(a),),
+            tag="gemv_bf16" if (M == 1 and ns == 1 and K >= 512 and K % 8 == 0) else
+            ((f"gemm_bf16_nt<{TILE_NAMES.get(tile, tile)}>" + ("+splitk" if ns > 1 else "")) if K % 64 == 0
+             else "small_linear") + (f" {M}x{n}x{K}" if PROFILER.detail else ""),
+            flops=2.0 * M * n * K, nbytes=2.0 * (M * K + n * K) + out.element_size() * M * n, dt=dt)
     return out
 
 
@@ -568,6 +567,18 @@ def gemv_batch_wins(M, N, K):
     output columns.  So: 2..4 rows, one staging pass, K <= 8192.  Round 6 (profiles/r06_decode_batch_ab.txt): with the fused
     RMSNorm in its one-round-trip form 3.51 / 3.65 / 3.76 ms at 2 / 3 / 4 sequences; 8 sequences still lose (4.47 vs 4.30)."""
     return _GEMV_BATCH_ON and 2 <= M <= GEMV_BATCH_ROWS and 512 <= K <= 8192 and K % 64 == 0 and M * (2 * K + 16) <= 98304
+
+
+def gemv_batch_ok(x, w, residual=None, out=None):
+    """gemv_batch may run x [B,K] x w [N,K]: the shape is one gemv_batch_wins names, the kernel can read the operands in 16-byte
+    pieces (addresses multiples of 16 bytes, row strides multiples of 8 elements, whole rows of x) and the residual is not
+    the output buffer (gemv_batch asserts that)."""
+    N, K = w.shape
+    if not gemv_batch_wins(len(x), N, K):
+        return False
+    ldx = x.stride(0)
+    return ldx % 8 == 0 and ldx >= K and w.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0 \
+        and (residual is None or out is None or residual.data_ptr() != out.data_ptr())
 
 
 _GEMV_BATCH_ON = os.environ.get("G4R_GEMV_BATCH", "1") != "0"      # (read once: gemm() sits in the eager decode loop)

@@ -595,14 +595,13 @@ class LlamaDecoder:
         scale = 1.0 / math.sqrt(D)
         work = self._attn_work(B)
         x = K.gather_rows(self.embed, st["tok32"])
-        fused = K.GEMV_BATCH_FUSED_NORM and K.gemv_batch_wins(B, 3 * C, C) and x.stride(0) % 8 == 0
 
         def norm_proj(x, gamma, w, h=None, **kw):
             """RMSNorm + projection: the normalised rows h when the previous launch already made them, else one launch on the
-            weight-streaming kernel (few rows), else two"""
+            weight-streaming kernel (few rows, operands it can read: the test gemm() applies), else two"""
             if h is not None:
                 return K.gemm(h, w, **kw)
-            if fused and K.gemv_batch_wins(B, w.size(0), C):
+            if K.GEMV_BATCH_FUSED_NORM and K.gemv_batch_ok(x, w):
                 return K.gemv_batch(x, w, norm_weight=gamma, eps=self.eps, variant=K.GEMV_BATCH_VARIANT, **kw)
             return K.gemm(K.rmsnorm(x, gamma, self.eps), w, **kw)
 

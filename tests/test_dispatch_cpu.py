@@ -1,7 +1,12 @@
 """CPU: the tile / split dispatch of the production shapes (pure host logic in gpt4roi_amd/kernels.py).  Every decision below
 was taken from an A/B measurement on MI355X (profiles/r02_gemm_tiles.md, r02_gemm_small_m.txt, r02_conv_k_order.jsonl,
 r05_w4k64_epilogue.txt: tile 34 replaces the ring ping-pong tile 24 on the 256 x 256 shapes); this test pins them so that a heuristic edit for one shape cannot silently move another."""
+import importlib.util
+import json
+import os
+
 import pytest
+import torch
 
 from gpt4roi_amd import kernels as K
 
@@ -65,3 +70,95 @@ def test_mlvl_maps_layout_is_level_major_with_contiguous_per_level_views():
     m.levels[1][1, 2, 0, 3] = 7.0                                 # level 1, image 1, y 2, x 0 -> flat row 60 + 9 + 6
     assert float(m.flat[60 + 9 + 6, 3]) == 7.0
     assert list(m._hw[0]) == [6, 3, 2] and list(m._hw[1]) == [5, 3, 1]
+
+
+# ---- gemm(): one routing plan (kernels.gemm_plan), replayed against the launches recorded before it existed ----
+
+@pytest.fixture(scope="module")
+def tracer(golden_dir):
+    """tests/golden/make_dispatch_golden.py: runs gemm() on meta / CPU operands with the launch recorded instead of issued"""
+    spec = importlib.util.spec_from_file_location("make_dispatch_golden", os.path.join(golden_dir, "make_dispatch_golden.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.fixture(scope="module")
+def golden(golden_dir):
+    with open(os.path.join(golden_dir, "gemm_dispatch.json")) as f:
+        return json.load(f)
+
+
+def _plan_strings(plan):
+    return [f"g:{p.n0}:{p.n1 - p.n0}" if p.kernel == "gemv_batch" else f"t{p.tile}:{p.n0}:{p.n1 - p.n0}:{p.splits}" for p in plan]
+
+
+def test_gemm_issues_the_recorded_launches_for_every_case(tracer, golden):
+    """Every case of the golden sweep (2662 shapes x BIG_TILE 34 / 24 x 16-bit / fp32 output x without / with residual, the swiglu
+    column splits, the operands the weight-streaming kernel refuses, the explicit tile_cfg / splits / workspace calls): the same
+    entry points with the same sizes, column offsets, tiles, K slices, profiler tags, flops and byte counts, and the same
+    answers of long_k_plan / small_m_split_plan / decode_split_plan / gemv_batch_wins."""
+    got = tracer.trace_all()
+    assert len(got["shapes"]) == len(golden["shapes"]) == len(tracer.MS) * len(tracer.NS) * len(tracer.KS)
+    assert len(got["extra"]) == len(golden["extra"])
+    for g, w in zip(got["shapes"] + got["extra"], golden["shapes"] + golden["extra"]):
+        assert g == w
+    plain = [len(c[6][int(c[7][i])].split(" ")) for c in golden["shapes"] for i in (0, 2)]
+    assert (plain.count(1), plain.count(2)) == (5198, 126)
+
+
+def test_the_plan_is_what_gemm_runs(tracer, golden, monkeypatch):
+    """gemm_plan's launch list equals the launches recorded from gemm(), for every case of the sweep and for the extra cases
+    that go through the planner."""
+    for M, N, Kd, _, _, _, uniq, idx in golden["shapes"]:
+        for (big, fp32, _), i in zip(tracer.VARIANTS, idx):
+            monkeypatch.setattr(K, "BIG_TILE", big)
+            assert " ".join(_plan_strings(K.gemm_plan(M, N, Kd, fp32_out=fp32, gemv_ok=True))) == uniq[int(i)], (M, N, Kd, big, fp32)
+    n_extra = 0
+    for name, launches in golden["extra"]:
+        what, shape = name.split(" ")[0], [w for w in name.replace(":", "").split(" ") if w.count("x") == 2][0]
+        M, N, Kd = (int(v) for v in shape.split("x"))
+        if what == "swiglu":                         # (the activation does not enter the plan: the weight rows are what it splits)
+            monkeypatch.setattr(K, "BIG_TILE", int(name.split("big")[1][:2]))
+            assert _plan_strings(K.gemm_plan(M, N, Kd, fp32_out=name.endswith("fp32=1"), gemv_ok=True)) == launches, name
+            n_extra += 1
+        elif what == "few":
+            monkeypatch.setattr(K, "BIG_TILE", 34)
+            f = launches[0].split(":")
+            plan = K.gemm_plan(M, N, Kd, fp32_out=False, gemv_ok=f[0] == "g")
+            assert len(launches) == len(plan) == 1 and plan[0].kernel == ("gemv_batch" if f[0] == "g" else "tile")
+            assert f[0] == "g" or (plan[0].tile, plan[0].splits) == (int(f[4]), int(f[5])), name
+            n_extra += 1
+    assert n_extra == 12 + 24
+
+
+def test_the_look_ahead_queries_answer_as_before_on_every_shape(tracer, golden):
+    """What llama.py (long_k_plan, decode_split_plan, gemv_batch_wins) and vit.py (small_m_split_plan) ask before they fuse a
+    K-slice reduce with the next norm: the recorded answer for each of the 2662 shapes at both BIG_TILE values.  With the test
+    above, no caller can be told anything but what gemm() runs."""
+    for M, N, Kd, q34, q24, *_ in golden["shapes"]:
+        assert (tracer.queries(M, N, Kd, 34), tracer.queries(M, N, Kd, 24)) == (q34, q24), (M, N, Kd)
+    assert K.long_k_plan(767, 4096, 11008) == (34, 4) and K.long_k_plan(1534, 4096, 11008) is None     # two merged requests: not fused
+    assert K.gemm_plan(1534, 4096, 11008)[0].rule == "partial_wave"
+    assert K.small_m_split_plan(577, 1024, 4096) == (14, 2) and K.decode_split_plan(8, 4096, 11008) == (14, 4)
+
+
+def test_gemv_batch_ok_refuses_operands_the_kernel_cannot_read():
+    def t(rows, cols, width=None, offset=0):
+        """bf16 [rows, cols] at a 64-byte aligned address + 2 * offset bytes, rows `width` elements apart"""
+        width = width or cols
+        buf = torch.zeros(rows * width + 64, dtype=torch.bfloat16)
+        lead = (-buf.data_ptr() % 64) // 2 + offset
+        return buf[lead:lead + rows * width].view(rows, width)[:, :cols]
+    x, w, out = t(4, 4096), t(256, 4096), t(4, 256)
+    assert K.gemv_batch_wins(4, 256, 4096)
+    assert K.gemv_batch_ok(x, w) and K.gemv_batch_ok(x, w, residual=t(4, 256), out=out) and K.gemv_batch_ok(x, w, out=out)
+    assert K.gemv_batch_ok(t(4, 4096, width=4104), w)                  # padded rows, still in 16-byte pieces
+    assert not K.gemv_batch_ok(t(4, 4096, width=4100), w)              # odd row stride
+    assert not K.gemv_batch_ok(x, t(256, 4096, width=4100))
+    assert not K.gemv_batch_ok(t(1, 4096).expand(4, 4096), w)          # stride(0) < K
+    assert not K.gemv_batch_ok(t(4, 4096, offset=1), w)                # address not a multiple of 16
+    assert not K.gemv_batch_ok(t(4, 4096, offset=4), w)
+    assert not K.gemv_batch_ok(x, t(256, 4096, offset=1))
+    assert not K.gemv_batch_ok(x, w, residual=out, out=out)            # residual aliasing out
+    assert not K.gemv_batch_ok(t(8, 4096), w)                          # a shape gemv_batch_wins does not name
