@@ -25,7 +25,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 
 
 # the inference path (ViT, region module, projector, splice, LLaMA prefill + decode); training-only files stay bf16
-F16_SOURCES = ("gemm_bf16.hip", "gemv_mfma.hip", "attention.hip", "attention_v2.hip", "norm.hip", "elementwise.hip", "roi_align.hip")
+F16_SOURCES = ("gemm_bf16.hip", "gemm_ring.hip", "gemm_pp32.hip", "gemm_w4k64.hip", "gemm_w4k64p.hip", "gemv_bf16.hip", "gemv_mfma.hip", "attention.hip", "attention_v2.hip", "norm.hip", "elementwise.hip", "roi_align.hip")
 F16_NAMES = os.path.join(os.path.dirname(HERE), "include", "g4r_f16_names.h")
 
 
@@ -41,6 +41,9 @@ def _newest_header():
 def build(verbose=False, force=False):
     os.makedirs(OBJ, exist_ok=True)
     srcs = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
+    missing = [s for s in F16_SOURCES if s not in srcs]
+    if missing:      # a misspelt name would silently drop that file's fp16 kernels from the library
+        raise RuntimeError(f"F16_SOURCES names files that are not in {CSRC}: {missing}")
     hdr_t = _newest_header()
     jobs, objs = [], []
     for s in srcs:
@@ -64,7 +67,7 @@ def build(verbose=False, force=False):
         if verbose and r.stderr.strip():
             print(r.stderr)
 
-    with ThreadPoolExecutor(max_workers=min(8, max(1, len(jobs)))) as ex:
+    with ThreadPoolExecutor(max_workers=min(16, max(1, len(jobs)))) as ex:
         list(ex.map(run, jobs))
     if jobs or not os.path.exists(LIB):
         run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", LIB])

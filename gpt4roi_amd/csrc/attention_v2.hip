@@ -58,7 +58,7 @@ __device__ __forceinline__ float a2_other_half(float x, bool want_max) {
 }
 
 // one 1 KiB LDS-DMA piece as buffer_load_dwordx4 ... lds (a free __device__ function: written inside a lambda of the kernel
-// the builtins make hipcc drop the kernel's host handle, see gemm_bf16.hip g4r_buffer_piece)
+// the builtins make hipcc drop the kernel's host handle, see gemm_common.h g4r_buffer_piece)
 __device__ __forceinline__ void a2_buffer_piece(const void* base, unsigned bytes, void* lds, int voff, int soff) {
   const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
   __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);

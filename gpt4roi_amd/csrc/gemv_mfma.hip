@@ -5,7 +5,7 @@
 //
 // What HF `generate()` computes per token for a batch of prompts (gpt4roi/app.py:293-300; SURVEY.md 8d config 5 decodes 8
 // requests together): LlamaRMSNorm + nn.Linear on [B, 1, K].  The step is HBM-bound (every 16-bit weight once per token for the
-// whole batch), so the kernel is built like the single-row GEMV (gemm_bf16.hip, gemv_bf16_kernel) and NOT like a GEMM tile:
+// whole batch), so the kernel is built like the single-row GEMV (gemv_bf16.hip, gemv_bf16_kernel) and NOT like a GEMM tile:
 //   * a workgroup owns 16 consecutive output rows n; its 8 waves split K in interleaved steps of 64 (two or four row blocks per
 //     workgroup -- fewer, fatter workgroups amortising the staged rows -- measured 1.4-3x slower: the kernel lives on the number of
 //     workgroups streaming);

@@ -162,3 +162,11 @@ def test_gemv_batch_ok_refuses_operands_the_kernel_cannot_read():
     assert not K.gemv_batch_ok(x, t(256, 4096, offset=1))
     assert not K.gemv_batch_ok(x, w, residual=out, out=out)            # residual aliasing out
     assert not K.gemv_batch_ok(t(8, 4096), w)                          # a shape gemv_batch_wins does not name
+
+
+def test_every_fp16_source_exists_and_a_misspelt_one_stops_the_build(monkeypatch):
+    from gpt4roi_amd import build
+    assert build.F16_SOURCES and all(os.path.isfile(os.path.join(build.CSRC, s)) for s in build.F16_SOURCES)
+    monkeypatch.setattr(build, "F16_SOURCES", build.F16_SOURCES + ("gemm_no_such_family.hip",))
+    with pytest.raises(RuntimeError, match="gemm_no_such_family.hip"):      # raised before any compile job starts
+        build.build()

@@ -2,7 +2,7 @@
 """tools/w4k64_check.py -- the round-5 one-wave-per-SIMD GEMM tile (tile_cfg 34) against the ring ping-pong tile (24) and
 fp32 torch arithmetic: dense shapes (ragged edges, one / two / three K tiles, K slices, every epilogue), the implicit-GEMM
 3x3 convolution (single map, groups, all pyramid levels in one launch), then timings (burst of 8, median of 5) of tiles 24 /
-26 / 34 and the vendor library on the bench's shapes.   python tools/w4k64_check.py [--no-time]"""
+34 and the vendor library on the bench's shapes.   python tools/w4k64_check.py [--no-time]"""
 import json
 import os
 import sys
@@ -134,7 +134,7 @@ for (M, N, Kd) in [(4096, 4096, 4096), (8192, 8192, 4096), (12272, 12288, 4096),
     a, w = R(M, Kd), R(N, Kd)
     out = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
     row = {"shape": [M, N, Kd]}
-    for t in (24, 26, 34):
+    for t in (24, 34):
         fn = lambda: K.gemm(a, w, out=out, tile_cfg=t)          # noqa: E731
         fn(); torch.cuda.synchronize()
         us = burst(fn)
