@@ -140,3 +140,100 @@ def dense_or_mask(attention_mask):
     if m.size(1) <= 1 or bool((m[:, :-1] | ~m[:, 1:]).all()):
         return None
     return m
+
+
+# ---- conversation sessions: a follow-up turn prefills only what the KV cache does not already hold -------------------
+def plan_reuse(cached_ids, new_ids, same_image, cached_boxes, new_boxes, bbox_id, max_positions, max_new_tokens):
+    """How many leading cache rows a new prompt may trust: -> L, the prompt is then prefilled from position L.
+
+    cached_ids: the token ids whose K/V the cache holds, in row order; new_ids: the new prompt; cached_boxes / new_boxes:
+    the box of every `<bbox>` token (id `bbox_id`) in order of appearance, as 4-number sequences.  L is
+      * the longest common prefix of the ids -- nothing is assumed about how the earlier answer re-tokenises: the caller
+        strips `###` / `Assistant:` from it (app.py:309-324) and the common prefix simply ends where that shows;
+      * 0 if the image differs (every patch token's embedding depends on it);
+      * cut to just before the first `<bbox>` position whose box differs (that row's embedding is the box's feature);
+      * at most len(new_ids) - 1: at least one token is prefilled, so logits exist;
+      * 0 if len(new_ids) + max_new_tokens does not fit the cache (the caller's full prefill then fails as it does today).
+    Pure host function."""
+    cached_ids, new_ids = list(cached_ids), list(new_ids)
+    if not same_image or not cached_ids or not new_ids:
+        return 0
+    if len(new_ids) + int(max_new_tokens) > int(max_positions):
+        return 0
+    n = min(len(cached_ids), len(new_ids) - 1)
+    L = 0
+    while L < n and cached_ids[L] == new_ids[L]:
+        L += 1
+    cached_boxes = [] if cached_boxes is None else list(cached_boxes)
+    new_boxes = [] if new_boxes is None else list(new_boxes)
+    k = 0
+    for p in range(L):
+        if new_ids[p] != bbox_id:
+            continue
+        same = k < len(cached_boxes) and k < len(new_boxes) and \
+            [float(x) for x in cached_boxes[k]] == [float(x) for x in new_boxes[k]]
+        if not same:
+            return p
+        k += 1
+    return L
+
+
+def _box_rows(bboxes):
+    """The boxes of a batch-1 request as a list of 4-float lists (bboxes: None, or the reference's list of one [n, 4])."""
+    if bboxes is None:
+        return []
+    if hasattr(bboxes, "boxes_h16"):                         # layers.PreparedBoxes: the rows the region module reads
+        rows = bboxes.boxes_h16
+    elif len(bboxes) == 0:
+        return []
+    else:
+        rows = bboxes[0]
+    return [[float(x) for x in row] for row in rows.detach().float().cpu().tolist()]
+
+
+class GenerationSession:
+    """What the KV cache of ONE decoder holds between the turns of ONE conversation, so that `generate(session=...)` can
+    prefill only the tokens behind the longest prefix it may trust (`plan_reuse`).  The caller keeps one per conversation,
+    next to the reference's `history_cache` (app.py), and hands it to every turn.
+
+    ids / image / boxes: the token ids whose K/V the cache holds (truncated to the decoder's row count), the image tensor
+    and the per-`<bbox>` boxes they were computed with.  decoder / stamp: the decoder they live in and its `cache_version`
+    when the session last wrote it -- a session that meets another decoder, or a cache somebody else has reset or written
+    since, is treated as empty.  reused / prefilled: cache rows kept / prompt positions prefilled by the last call."""
+
+    def __init__(self):
+        self.clear()
+        self.reused = 0
+        self.prefilled = 0
+
+    def clear(self):
+        self.ids, self.image, self.boxes, self.decoder, self.stamp = [], None, [], None, None
+
+    def valid_for(self, decoder):
+        return (self.decoder is decoder and self.stamp is not None and self.stamp == getattr(decoder, "cache_version", None)
+                and len(self.ids) > 0 and len(self.ids) <= getattr(decoder, "rows_held", 0))
+
+    def same_image(self, image):
+        """Pixels are compared with the session's own copy (an in-place change by the caller shows).  A turn without an
+        image trusts nothing: a text-only conversation runs as without a session."""
+        if self.image is None or image is None:
+            return False
+        return self.image.shape == image.shape and self.image.dtype == image.dtype and \
+            self.image.device == image.device and bool(torch.equal(self.image, image))
+
+    def plan(self, decoder, new_ids, image, boxes, bbox_id, max_new_tokens):
+        """-> L for this turn (0 for an empty / foreign / stale session)."""
+        if not self.valid_for(decoder):
+            return 0
+        return plan_reuse(self.ids, new_ids, self.same_image(image), self.boxes, boxes, bbox_id, decoder.max_positions,
+                          max_new_tokens)
+
+    def update(self, decoder, prompt_ids, new_ids, image, boxes, reused):
+        """After a decode: the cache holds the prompt and the generated tokens that were fed back (`decoder.rows_held`)."""
+        prompt_ids = list(prompt_ids)
+        self.ids = (prompt_ids + list(new_ids))[:int(decoder.rows_held)]
+        if image is None or not self.same_image(image):
+            self.image = None if image is None else image.detach().clone()
+        self.boxes = [list(b) for b in boxes]
+        self.decoder, self.stamp = decoder, decoder.cache_version
+        self.reused, self.prefilled = int(reused), len(prompt_ids) - int(reused)

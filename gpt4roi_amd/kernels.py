@@ -22,6 +22,8 @@ _SIGS = {
     "g4r_flash_attn_fwd_bf16": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_long, c_long, c_long, c_long,
                                 c_long, c_long, c_long, c_long, c_float, c_int, P, P, P],
     "g4r_conv3x3_mlvl_nhwc_bf16": [P, P, P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, P],
+    "g4r_flash_attn_cont_bf16": [P, P, P, P, P, c_long, c_int, c_int, c_int, c_int, c_int, c_long, c_long, c_long, c_long,
+                                 c_long, c_long, c_long, c_long, c_float, c_int, P],
     "g4r_batch_advance": [P, c_int, P, P, P, P, P, c_int, P],
     "g4r_gemv_rmsnorm_bf16": [P, P, c_float, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P],
     "g4r_gemv_batch_bf16": [P, c_int, c_long, P, c_float, P, P, c_long, P, P, c_long, c_int, c_int, c_int, c_int, c_int, c_int, P],
@@ -699,6 +701,66 @@ def flash_attn(q, k, v, heads, scale, causal=False, out=None, kv_len_dev=None, l
         _p(lse), _stream(q),),
         tag=f"flash_attn<{D}>", flops=4.0 * B * heads * Tq * Tk * D * (0.5 if causal and Tq == Tk else 1.0),
         nbytes=2.0 * B * HD * (2 * Tq + 2 * Tk), dt=dt)
+    return out
+
+
+CONT_MAX_TQ = 64            # query rows g4r_flash_attn_cont_bf16 takes (one 64-row block stays in registers)
+
+
+def cont_splits(heads, batch, Tk):
+    """Key splits of flash_attn_cont: enough workgroups (heads x splits x batch) for the 256 CUs, at most 8 (each split
+    leaves a [64, D + 2] fp32 partial per head), and no more than there are 64-key tiles."""
+    return max(1, min(8, 256 // max(1, heads * batch), -(-Tk // 64)))
+
+
+CONT_ATTN_ROUTE = "rule"    # "rule" = the measured routing rule below; "always" / "never" pin a route (tools, tests)
+
+
+def cont_attn_wins(Tq, Tk, heads, batch=1, head_dim=128):
+    """Routing rule of a prefill chunk behind a cached prefix (LlamaDecoder.forward with pos0 > 0): whether its attention
+    runs on the split-key kernel (flash_attn_cont) instead of the prefill forward.  The kernel is adopted only where a
+    hipGraph-timed A/B against the forward shows a win beyond the forward's own run-to-run spread (tools/session_bench.py
+    --kernel, profiles/session_kernel_ab.txt: H = 32, D = 128, B = 1, Tq 8-64 x Tk 512-2048, both dtypes).  It wins at every
+    measured point with Tk >= 32 Tq (1.2-2.8x) and at none of the others (Tq 32 / Tk 512, Tq 64 / Tk 512 and 1024), so that
+    line is the rule, for the measured head count and Tk >= 512 only."""
+    applies = 2 <= Tq <= CONT_MAX_TQ and Tk > Tq and head_dim in (64, 128)
+    if CONT_ATTN_ROUTE != "rule":
+        return applies and CONT_ATTN_ROUTE == "always"
+    return applies and heads * batch == 32 and head_dim == 128 and Tk >= 512 and Tk >= 32 * Tq
+
+
+class ContAttnWorkspace:
+    """fp32 partials of flash_attn_cont for up to `batch` sequences and `splits` key splits.  Plain scratch: a call leaves
+    nothing in it that the next call reads, so one per decoder serves every layer (the layers run back to back on one
+    stream)."""
+
+    def __init__(self, heads, head_dim, device, splits=8, batch=1):
+        self.heads, self.head_dim, self.splits, self.batch = heads, head_dim, splits, batch
+        self.ws = torch.empty(batch * heads * splits * CONT_MAX_TQ * (head_dim + 2), dtype=torch.float32, device=device)
+
+
+def flash_attn_cont(q, k, v, heads, scale, work=None, out=None, splits=None):
+    """Causal attention of a short query block against a long cache, keys split over workgroups (csrc/attention_cont.hip):
+    q [B, Tq <= 64, heads*D], k/v [B, Tk >= Tq, heads*D] row-strided cache views -> [B, Tq, heads*D]; query i sees keys
+    <= i + (Tk - Tq).  work: a ContAttnWorkspace (allocated here when None); splits: key splits (default cont_splits)."""
+    dt = _h16(q, k, v)
+    B, Tq, HD = q.shape
+    Tk = k.size(1)
+    D = HD // heads
+    assert q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1 and v.size(1) == Tk
+    if not 1 <= Tq <= CONT_MAX_TQ or Tk < Tq:
+        raise ValueError(f"flash_attn_cont takes 1 <= Tq <= {CONT_MAX_TQ} and Tk >= Tq, got Tq = {Tq}, Tk = {Tk}")
+    S = int(splits) if splits else cont_splits(heads, B, Tk)
+    if work is None:
+        work = ContAttnWorkspace(heads, D, q.device, splits=S, batch=B)
+    _f32(work.ws)
+    if out is None:
+        out = torch.empty((B, Tq, HD), dtype=dt, device=q.device)
+    assert out.dtype == dt and out.stride(2) == 1
+    _launch("g4r_flash_attn_cont_bf16", (
+        _p(q), _p(k), _p(v), _p(out), _p(work.ws), work.ws.numel(), B, heads, Tq, Tk, D, q.stride(1), k.stride(1),
+        v.stride(1), out.stride(1), q.stride(0), k.stride(0), v.stride(0), out.stride(0), float(scale), S, _stream(q),),
+        tag=f"flash_attn_cont<{D}>", flops=4.0 * B * heads * Tq * Tk * D, nbytes=2.0 * B * HD * (2 * Tq + 2 * Tk), dt=dt)
     return out
 
 

@@ -128,12 +128,39 @@ class LlamaDecoder:
         self.ragged = None             # RaggedLayout of the prompt in the cache (pad rows squeezed out), or None
         self._dstate = None            # a captured decode graph points into the old cache
         self._bstate = None
+        self.rows_held = 0             # cache rows of sequence 0 that hold the K/V of known tokens (see `rewind`)
+        self.cache_version = getattr(self, "cache_version", 0) + 1   # moves whenever the cache content does
 
     def reset(self, batch=1):
         if self.kc.size(1) < batch:
             self._alloc_cache(batch)
         self.pos = 0
         self.ragged = None
+        self.rows_held = 0
+        self.cache_version += 1
+
+    def rewind(self, L):
+        """Continue from a cache prefix: the first L rows of sequence 0 stay, the next `forward` appends at position L.
+        For the dense batch-1 layout only (a ragged layout shares one RoPE position per step, which a continuation would
+        break), and L may not exceed `rows_held`, the rows the last calls actually wrote."""
+        L = int(L)
+        if self.ragged is not None:
+            raise ValueError("rewind: the cache holds a ragged (masked) batch; only the dense batch-1 layout continues")
+        if not 0 <= L <= self.rows_held:
+            raise ValueError(f"rewind({L}): the cache holds {self.rows_held} rows")
+        self.pos = L
+        self.rows_held = L
+        self.cache_version += 1
+
+    def _cont_work(self, batch=1):
+        """Partials workspace of the split-key continuation attention (kernels.flash_attn_cont), one per batch size."""
+        pool = getattr(self, "_cont_ws", None)
+        if pool is None:
+            pool = self._cont_ws = {}
+        if batch not in pool:
+            with torch.inference_mode(False):
+                pool[batch] = K.ContAttnWorkspace(self.heads, self.head_dim, self.device, splits=8, batch=batch)
+        return pool[batch]
 
     def _attn_ragged(self, li, q, rag, want_lse=False, compact=False):
         """Causal attention of a masked batch (see RaggedLayout): q [B, T, C] rotated, K/V of this layer already in the
@@ -212,6 +239,10 @@ class LlamaDecoder:
                         K.rope_qkv(qkv[b], self.cos, self.sin, q[b], self.kc[li, b], self.vc[li, b], H, D, pos0)
                 if rag is not None:
                     a, _ = self._attn_ragged(li, q, rag, compact=True)
+                elif pos0 > 0 and K.cont_attn_wins(T, pos0 + T, H, B, D):
+                    # a short chunk behind a long cached prefix (the follow-up turn of a session): keys split over workgroups
+                    a = K.flash_attn_cont(q, self.kc[li, :B, :pos0 + T], self.vc[li, :B, :pos0 + T], H, scale,
+                                          work=self._cont_work(B))
                 else:
                     a = K.flash_attn(q, self.kc[li, :B, :pos0 + T], self.vc[li, :B, :pos0 + T], H, scale, True)
             x = K.gemm(a.view(B * T, C), L['wo'], residual=x)
@@ -228,6 +259,8 @@ class LlamaDecoder:
                 x = K.gemm(f, L['wd'], residual=x)
                 h = None
         self.pos = pos0 + T
+        self.rows_held = self.pos if (B == 1 and self.ragged is None) else 0
+        self.cache_version += 1
         if T == 1 and self.ragged is not None:
             self._rag_pos += 1
         xn = (h if h is not None else K.rmsnorm(x, self.norm, self.eps)).view(B, T, C)
@@ -373,6 +406,8 @@ class LlamaDecoder:
         xn = K.rmsnorm(x, self.norm, self.eps)
         logits = K.gemm(xn, self.lm_head, out_dtype=torch.float32)
         self.pos = T
+        self.rows_held = 0
+        self.cache_version += 1
         return logits, dict(B=B, T=T, saved=saved, x_final=x, xn=xn, checkpoint=checkpoint, rag=rag)
 
     def backward(self, ctx, dlogits, on_grad=None, grad_slot=None):
@@ -525,15 +560,25 @@ class LlamaDecoder:
 
     @torch.no_grad()
     def decode_graph(self, inputs_embeds, max_new_tokens, stop_ids=(), check_every=32, use_graph=True, sampler=None,
-                     seed=0, on_tokens=None):
+                     seed=0, on_tokens=None, past_len=0):
         """generate() for batch 1 with the per-token loop on the device: prefill eagerly, then replay one captured
         hipGraph per token (token id, position, output slot, sampling seed and step live in device memory).
         sampler = None (greedy) or (temperature, top_k, top_p); the uniform of step s is Philox(seed, s).
         The host looks at the ids every `check_every` tokens: `stop_ids` ends the sequence at the first hit
-        (inclusive); `on_tokens(list of new ids) -> bool` is the hook for HF-style stopping criteria."""
+        (inclusive); `on_tokens(list of new ids) -> bool` is the hook for HF-style stopping criteria.
+        past_len = L > 0: the first L cache rows already hold the K/V of inputs_embeds[:, :L] (see `rewind`): no reset, only
+        inputs_embeds[:, L:] is prefilled, at position L; everything after the prefill is the same.  Afterwards `rows_held`
+        says how many cache rows hold known tokens: the prompt and every generated token but the last (never fed back)."""
         assert inputs_embeds.size(0) == 1
-        self.reset(1)
-        logits = self.forward(inputs_embeds, all_logits=False)
+        past_len = int(past_len)
+        if past_len > 0:
+            if not past_len < inputs_embeds.size(1):
+                raise ValueError(f"past_len = {past_len} leaves nothing of the {inputs_embeds.size(1)} positions to prefill")
+            self.rewind(past_len)
+            logits = self.forward(inputs_embeds[:, past_len:], all_logits=False)
+        else:
+            self.reset(1)
+            logits = self.forward(inputs_embeds, all_logits=False)
         T = self.pos
         assert T + max_new_tokens <= self.max_positions
         st = self._decode_state(max_new_tokens)
@@ -582,6 +627,8 @@ class LlamaDecoder:
         if end is not None:
             done = end
         self.pos = T + done
+        self.rows_held = T + done - 1                    # the last token was not fed back
+        self.cache_version += 1
         return st["out"][:done].tolist()
 
     def greedy_graph(self, inputs_embeds, max_new_tokens, stop_ids=(), check_every=32, use_graph=True):

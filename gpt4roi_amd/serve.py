@@ -138,8 +138,11 @@ class ConversationBot:
         return None, text
 
     # ---- one round: model ------------------------------------------------------------------------------------------
-    def run(self, text, image, history_cache, do_sample=True, temperature=0.2, max_new_tokens=1024, seed=None):
-        """One question -> (answer text or None, error message or None, history_cache)   (app.py:243-328, no UI state)."""
+    def run(self, text, image, history_cache, do_sample=True, temperature=0.2, max_new_tokens=1024, seed=None,
+            session=None):
+        """One question -> (answer text or None, error message or None, history_cache)   (app.py:243-328, no UI state).
+        session: a generation.GenerationSession the caller keeps next to `history_cache`, one per conversation; with it a
+        follow-up turn prefills only the tokens the KV cache does not hold yet (same answers, see generate)."""
         error, text = self.check_input(text, image, history_cache)
         if error is not None:
             return None, error, history_cache
@@ -159,7 +162,7 @@ class ConversationBot:
             try:
                 output_ids = model.generate(input_ids, images=inputs['image'][None].to(self.device), do_sample=do_sample,
                                             temperature=temperature, max_new_tokens=max_new_tokens,
-                                            stopping_criteria=[criteria], seed=seed)
+                                            stopping_criteria=[criteria], seed=seed, session=session)
             finally:
                 model.forward = model.orig_forward
         T = input_ids.shape[1]

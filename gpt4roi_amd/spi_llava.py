@@ -38,8 +38,8 @@ import torch
 import torch.nn as nn
 
 from . import kernels as K
-from .generation import (KeywordsStoppingCriteria, SamplingConfig, StoppingCriteria,  # noqa: F401 (re-exported)
-                         dense_or_mask, expand_seeds, prepare_inputs_for_generation)
+from .generation import (GenerationSession, KeywordsStoppingCriteria, SamplingConfig,  # noqa: F401 (re-exported)
+                         StoppingCriteria, _box_rows, dense_or_mask, expand_seeds, prepare_inputs_for_generation)
 from .layers import MLVLROIQueryModule, PreparedBoxes
 from .llama import LlamaDecoder
 from .vit import ClipVisionTower
@@ -611,7 +611,7 @@ class SPILlavaMPTForCausalLM(nn.Module):
     @torch.no_grad()
     def generate(self, input_ids=None, images=None, max_new_tokens=64, do_sample=None, temperature=None, top_k=None,
                  top_p=None, stopping_criteria=None, eos_token_id=None, seed=None, bboxes=None, stop_ids=(),
-                 check_every=None, return_new_tokens=False, attention_mask=None, pad_token_id=None, **_):
+                 check_every=None, return_new_tokens=False, attention_mask=None, pad_token_id=None, session=None, **_):
         """HF-style `generate`.  Batch 1 (what gpt4roi/app.py:293-300 calls): prefill through `self.forward` -- so a
         `partial(orig_forward, img_metas=..., bboxes=...)` bound by the caller is honoured (app.py:286-291; `bboxes=`
         may also be passed here) -- then the device-resident decode loop.  do_sample=False: greedy (the parity mode);
@@ -629,7 +629,14 @@ class SPILlavaMPTForCausalLM(nn.Module):
         once with the prompt (row 0, [1, T]: KeywordsStoppingCriteria records its start length there), then with each
         row's own [1, T + n] ids (padded prompt + that row's new ids); a row stops at the first token for which any
         criterion returns true, and the decode ends when every row has stopped -- a request merged into a batch behaves
-        as if it were served alone."""
+        as if it were served alone.
+        session (batch 1 only): a generation.GenerationSession kept by the caller for one conversation.  The vision path
+        and the splice run as always; then only the prompt positions behind the longest cache prefix the session may
+        trust (generation.plan_reuse: same ids, same image, same boxes) are prefilled, and the session is updated with
+        what the cache holds afterwards.  Sampling, seeds, stopping and the return value are those of a call without it."""
+        if session is not None and input_ids.size(0) > 1:
+            raise ValueError(f"generate(session=...) continues ONE conversation; got a batch of {input_ids.size(0)} sequences "
+                             "(batched and ragged continuation is not supported: call without a session)")
         if input_ids.size(0) > 1:
             return self._generate_batch(input_ids, images, max_new_tokens, do_sample, temperature, top_k, top_p, seed,
                                         stopping_criteria, eos_token_id, bboxes, stop_ids, check_every, return_new_tokens,
@@ -669,8 +676,16 @@ class SPILlavaMPTForCausalLM(nn.Module):
             # the first call above consumed HF's "first token" call of the reference criteria (start_len recorded),
             # so token 1 is tested like every later one
         every = check_every if check_every is not None else (1 if stopping_criteria else 32)
+        past = 0
+        if session is not None:
+            bound = getattr(fwd, "keywords", None) or {}
+            boxes = _box_rows(kw.get("bboxes", bound.get("bboxes")))
+            prompt_ids = input_ids[0].tolist()
+            past = session.plan(dec, prompt_ids, images, boxes, self.model.config.bbox_token, max_new_tokens)
         new = dec.decode_graph(embeds, max_new_tokens, stop_ids=stops, check_every=every, sampler=sampler, seed=seed,
-                               on_tokens=on_tokens)
+                               on_tokens=on_tokens, past_len=past)
+        if session is not None:
+            session.update(dec, prompt_ids, new, images, boxes, past)
         if return_new_tokens:
             return new
         return torch.cat([input_ids, torch.tensor([new], dtype=input_ids.dtype, device=input_ids.device)], 1)

@@ -82,6 +82,23 @@ int g4r_flash_attn_fwd_bf16(const void* Q, const void* K, const void* V, void* O
                             int causal, const int* kv_len_dev, float* lse, void* stream);
 
 /*
+ * Causal attention of a SHORT query block against a LONG KV cache: the prefill of a follow-up turn whose earlier tokens
+ * are already cached (the conversation loop of gpt4roi/app.py re-sends `history_cache` every turn).  1 <= Tq <= 64 rows of
+ * Q [B, Tq, H*D]; K/V = the first Tk >= Tq rows of cache views [B, T_max, H*D]; O [B, Tq, H*D]; strides in elements as for
+ * g4r_flash_attn_fwd_bf16; query i attends keys <= i + (Tk - Tq); head_dim 64 or 128.  The key tiles (64 keys) are cut
+ * into `splits` (1..64) runs, one workgroup per (run, head, sequence); each leaves an fp32 partial (acc, max, sum) in
+ * `workspace` and a second launch inside the call merges them.  workspace: at least B*H*splits*64*(head_dim+2) floats
+ * (`workspace_floats` = its size), 16-byte aligned, owned by the caller; it carries no state from one call to the next.
+ * Q, K, V must be 16-byte aligned and O 8-byte aligned (so must every row: strides are checked).  Agrees with
+ * g4r_flash_attn_fwd_bf16 (causal) within 16-bit rounding, not bit for bit: the probabilities enter the PV product as a
+ * 16-bit value plus their 16-bit rounding residual (the forward rounds them once), and the splits are summed in fp32.
+ */
+int g4r_flash_attn_cont_bf16(const void* Q, const void* K, const void* V, void* O, float* workspace, long workspace_floats,
+                             int B, int H, int Tq, int Tk, int head_dim, long q_row, long k_row, long v_row, long o_row,
+                             long q_batch, long k_batch, long v_batch, long o_batch, float scale, int splits,
+                             void* stream);
+
+/*
  * One activation row through a projection, with the RMSNorm in front of it fused in: the per-token form of
  * `LlamaRMSNorm` + `nn.Linear` that the decode loop of gpt4roi/app.py:293-300 runs 4x per layer (HF LlamaDecoderLayer).
  *   C [N] = act(W [N, K] . h + bias) + residual,  h = gamma ? bf16(bf16(x * rsqrt(mean(x^2) + eps)) * gamma) : x
