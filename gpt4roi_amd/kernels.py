@@ -1344,7 +1344,9 @@ class MultiTensorAdamW:
     gradient pointers are re-uploaded only when they change (they are stable when the bucketed reducer owns them)."""
     CHUNK = 4096
 
-    def __init__(self, params, bf16_copies=None, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    def __init__(self, params, bf16_copies=None, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, moments=None):
+        """moments: (exp_avg list, exp_avg_sq list) of contiguous fp32 tensors to adopt as the state instead of allocating
+        zeros (a caller that owns the storage: the tests place it between guard elements)."""
         self.params = list(params)
         _f32(*self.params)
         for p in self.params:
@@ -1356,8 +1358,13 @@ class MultiTensorAdamW:
             if c is not None:
                 _bf16(c)
                 assert c.is_contiguous() and c.numel() == p.numel()
-        self.exp_avg = [torch.zeros_like(p) for p in self.params]
-        self.exp_avg_sq = [torch.zeros_like(p) for p in self.params]
+        if moments is None:
+            moments = ([torch.zeros_like(p) for p in self.params], [torch.zeros_like(p) for p in self.params])
+        self.exp_avg, self.exp_avg_sq = list(moments[0]), list(moments[1])
+        assert len(self.exp_avg) == len(self.params) and len(self.exp_avg_sq) == len(self.params)
+        _f32(*self.exp_avg, *self.exp_avg_sq)
+        for p, m, v in zip(self.params, self.exp_avg, self.exp_avg_sq):
+            assert m.is_contiguous() and v.is_contiguous() and m.numel() == p.numel() and v.numel() == p.numel()
         self.betas, self.eps, self.weight_decay = betas, eps, weight_decay
         self.steps = 0
         i64 = lambda xs: torch.tensor(xs, dtype=torch.int64, device=dev)  # noqa: E731

@@ -13,6 +13,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 import _mp
+from _optim_ref import torch_adamw_slice
 from gpt4roi_amd.fsdp import FullShardManager
 
 LR, CLIP, BETAS, EPS = 1e-2, 1.0, (0.9, 0.999), 1e-8
@@ -40,16 +41,9 @@ def _grad(name, shape, rank, step):
 
 
 def torch_update(f, lr, step, betas, eps, wd, total_sq, max_norm):
-    """AdamW on one flat slice in plain torch (the fused HIP kernels need the GPU)."""
-    g = f.grad_shard.clone()
-    if total_sq is not None:
-        coef = min(1.0, max_norm / (float(total_sq.sqrt()) + 1e-6))
-        g = g * coef
-    f.exp_avg.mul_(betas[0]).add_(g, alpha=1 - betas[0])
-    f.exp_avg_sq.mul_(betas[1]).addcmul_(g, g, value=1 - betas[1])
-    bc1, bc2 = 1 - betas[0] ** step, 1 - betas[1] ** step
-    denom = (f.exp_avg_sq / bc2).sqrt() + eps
-    f.master.mul_(1 - lr * wd).addcdiv_(f.exp_avg / bc1, denom, value=-lr)
+    """clip + AdamW on one flat slice: the torch restatement shared with tests/test_sharded_gloo.py (the fused HIP kernels
+    need the GPU)."""
+    torch_adamw_slice(f.master, f.exp_avg, f.exp_avg_sq, f.grad_shard, lr, step, betas, eps, wd, total_sq, max_norm)
     if f.param_shard.dtype != torch.float32:
         f.param_shard.copy_(f.master)
 

@@ -14,6 +14,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 import _mp
+from _optim_ref import torch_adamw_slice
 
 from gpt4roi_amd.sharded import ShardedAdamW
 
@@ -40,20 +41,10 @@ def _grad(i, shape, rank, step):
 
 
 def torch_update(b, lr, step, betas, eps, wd, total_sq, max_norm):
-    """AdamW on the owned shard of one bucket, torch ops (the math of g4r_multi_adamw_f32)."""
-    g = b.grad_shard
-    if total_sq is not None:
-        coef = max_norm / (float(total_sq.sqrt()) + 1e-6)
-        if coef < 1.0:
-            g = g * coef
-    p = b.master
-    b.exp_avg.mul_(betas[0]).add_(g, alpha=1 - betas[0])
-    b.exp_avg_sq.mul_(betas[1]).addcmul_(g, g, value=1 - betas[1])
-    p.mul_(1 - lr * wd)
-    denom = (b.exp_avg_sq / (1 - betas[1] ** step)).sqrt_().add_(eps)
-    p.addcdiv_(b.exp_avg / (1 - betas[0] ** step), denom, value=-lr)
+    """clip + AdamW on the owned shard of one bucket: the torch restatement shared with tests/test_fsdp_gloo.py."""
+    torch_adamw_slice(b.master, b.exp_avg, b.exp_avg_sq, b.grad_shard, lr, step, betas, eps, wd, total_sq, max_norm)
     if b.live_dtype == torch.bfloat16:
-        b.param_shard.copy_(p)
+        b.param_shard.copy_(b.master)
 
 
 def _worker(rank, world, port, q):
