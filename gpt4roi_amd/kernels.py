@@ -1189,44 +1189,86 @@ def flash_attn_bwd(q, k, v, o, do, lse, heads, scale, causal=True, out=None):
     return dq, dk, dv
 
 
-def rmsnorm_bwd(x, gamma, dy, dres=None, dgamma=None, eps=1e-6):
-    """dx = dres + d rmsnorm(x; gamma)/dx . dy; x, dy, dres [rows, cols] bf16 (row-strided ok)."""
-    _bf16(x, dy, dres)
+def _rows_arg(op, name, t, rows=None, cols=None):
+    """`t` is what a row kernel indexes as t[r * stride(0) + c]: 2-D, unit inner stride, of the shape the call implies
+    (None = not fixed by the call).  ValueError before anything is launched: the kernels trust their strides."""
+    if t is None:
+        return
+    if t.dim() != 2:
+        raise ValueError(f"{op}: {name} must be 2-D, got shape {tuple(t.shape)}")
+    if t.stride(1) != 1 and t.size(1) > 1:
+        raise ValueError(f"{op}: {name} must have unit inner stride, got strides {tuple(t.stride())}")
+    if (rows is not None and t.size(0) != rows) or (cols is not None and t.size(1) != cols):
+        want = f"[{'*' if rows is None else rows}, {'*' if cols is None else cols}]"
+        raise ValueError(f"{op}: {name} must be {want}, got shape {tuple(t.shape)}")
+
+
+def _vec_arg(op, name, t, n):
+    """`t` is read or written as n consecutive values."""
+    if t is not None and (t.numel() != n or not t.is_contiguous()):
+        raise ValueError(f"{op}: {name} must hold {n} contiguous values, got shape {tuple(t.shape)} "
+                         f"strides {tuple(t.stride())}")
+
+
+def rmsnorm_bwd(x, gamma, dy, dres=None, dgamma=None, eps=1e-6, out=None):
+    """dx = dres + d rmsnorm(x; gamma)/dx . dy; x, dy, dres [rows, cols] bf16 (row-strided ok).  dgamma fp32 [cols] is
+    accumulated into.  `out`: a [rows, cols] bf16 view (row-strided ok) that receives dx."""
+    _bf16(x, dy, dres, out)
     _f32(gamma, dgamma)
+    _rows_arg("rmsnorm_bwd", "x", x)
     rows, cols = x.shape
-    dx = torch.empty((rows, cols), dtype=torch.bfloat16, device=x.device)
+    _rows_arg("rmsnorm_bwd", "dy", dy, rows, cols)
+    _rows_arg("rmsnorm_bwd", "dres", dres, rows, cols)
+    _rows_arg("rmsnorm_bwd", "out", out, rows, cols)
+    _vec_arg("rmsnorm_bwd", "gamma", gamma, cols)
+    _vec_arg("rmsnorm_bwd", "dgamma", dgamma, cols)
+    dx = torch.empty((rows, cols), dtype=torch.bfloat16, device=x.device) if out is None else out
     _launch("g4r_rmsnorm_bwd_bf16", (_p(x), _p(gamma), _p(dy), _p(dres), _p(dx), _p(dgamma), rows, cols, x.stride(0),
                                      dy.stride(0), dres.stride(0) if dres is not None else 0, dx.stride(0),
                                      float(eps), _stream(x),), tag="g4r_rmsnorm_bwd_bf16")
     return dx
 
 
-def layernorm_bwd(x, gamma, dy, dgamma=None, dbeta=None, eps=1e-5, relu_in=False, need_dx=True):
-    _bf16(x, dy)
+def layernorm_bwd(x, gamma, dy, dgamma=None, dbeta=None, eps=1e-5, relu_in=False, need_dx=True, out=None):
+    """x, dy [rows, cols] bf16 (row-strided ok); dgamma, dbeta fp32 [cols] are accumulated into.  need_dx=False: only the
+    parameter gradients (returns None).  `out`: a [rows, cols] bf16 view (row-strided ok) that receives dx."""
+    _bf16(x, dy, out)
     _f32(gamma, dgamma, dbeta)
+    _rows_arg("layernorm_bwd", "x", x)
     rows, cols = x.shape
-    dx = torch.empty((rows, cols), dtype=torch.bfloat16, device=x.device) if need_dx else None
+    _rows_arg("layernorm_bwd", "dy", dy, rows, cols)
+    _rows_arg("layernorm_bwd", "out", out, rows, cols)
+    _vec_arg("layernorm_bwd", "gamma", gamma, cols)
+    _vec_arg("layernorm_bwd", "dgamma", dgamma, cols)
+    _vec_arg("layernorm_bwd", "dbeta", dbeta, cols)
+    if out is not None and not need_dx:
+        raise ValueError("layernorm_bwd: out given with need_dx=False")
+    dx = None
+    if need_dx:
+        dx = torch.empty((rows, cols), dtype=torch.bfloat16, device=x.device) if out is None else out
     _launch("g4r_layernorm_bwd_bf16", (_p(x), _p(gamma), _p(dy), _p(dx), _p(dgamma), _p(dbeta), rows, cols,
                                        x.stride(0), dy.stride(0), dx.stride(0) if need_dx else 0, float(eps),
                                        int(bool(relu_in)), _stream(x),), tag="g4r_layernorm_bwd_bf16")
     return dx
 
 
-def swiglu_il(gu):
-    """gu [T, 2F] with interleaved (gate, up) columns -> silu(gate) * up [T, F]."""
-    _bf16(gu)
+def swiglu_il(gu, out=None):
+    """gu [T, 2F] with interleaved (gate, up) columns -> silu(gate) * up [T, F] (`out`: a dense [T, F] view to fill)."""
+    _bf16(gu, out)
     T, F2 = gu.shape
-    out = torch.empty((T, F2 // 2), dtype=torch.bfloat16, device=gu.device)
-    assert gu.is_contiguous()
+    if out is None:
+        out = torch.empty((T, F2 // 2), dtype=torch.bfloat16, device=gu.device)
+    assert gu.is_contiguous() and out.is_contiguous() and out.shape == (T, F2 // 2)
     _launch("g4r_swiglu_il_bf16", (_p(gu), _p(out), T, F2 // 2, _stream(gu),), tag="g4r_swiglu_il_bf16")
     return out
 
 
-def swiglu_il_bwd(gu, dy):
-    _bf16(gu, dy)
+def swiglu_il_bwd(gu, dy, out=None):
+    _bf16(gu, dy, out)
     T, F2 = gu.shape
     assert gu.is_contiguous() and dy.is_contiguous() and dy.shape == (T, F2 // 2)
-    dgu = torch.empty_like(gu)
+    dgu = torch.empty_like(gu) if out is None else out
+    assert dgu.is_contiguous() and dgu.shape == gu.shape
     _launch("g4r_swiglu_il_bwd_bf16", (_p(gu), _p(dy), _p(dgu), T, F2 // 2, _stream(gu),),
             tag="g4r_swiglu_il_bwd_bf16")
     return dgu
@@ -1234,22 +1276,35 @@ def swiglu_il_bwd(gu, dy):
 
 def rope_qkv_bwd(dq, dk, dv, cos, sin, heads, head_dim, pos0=0, out=None, period=0):
     """dq, dk, dv [T, heads*D] (row-strided ok) -> d(qkv) [T, 3*heads*D] (`out`: a dense [T, 3*heads*D] view to fill).
-    period > 0: the rows are B stacked sequences of `period` tokens each (positions restart): one launch for the batch."""
-    _bf16(dq, dk, dv)
+    period > 0: the rows are B stacked sequences of `period` tokens each (positions restart): one launch for the batch.
+    cos, sin: fp32 [>= pos0 + T (or pos0 + period), D/2], dense."""
+    _bf16(dq, dk, dv, out)
+    _f32(cos, sin)
+    op = "rope_qkv_bwd"
+    _rows_arg(op, "dq", dq, None, heads * head_dim)
     T, HD = dq.shape
+    _rows_arg(op, "dk", dk, T, HD)
+    _rows_arg(op, "dv", dv, T, HD)
+    period, pos0 = int(period), int(pos0)
+    if period < 0 or pos0 < 0 or (period and T % period):
+        raise ValueError(f"{op}: {T} rows are no whole number of sequences of period {period} (pos0 {pos0})")
+    span = pos0 + (period if period else T)
+    for name, tab in (("cos", cos), ("sin", sin)):
+        _rows_arg(op, name, tab, None, head_dim // 2)
+        if not tab.is_contiguous():
+            raise ValueError(f"{op}: {name} must be dense, got strides {tuple(tab.stride())}")
+        if tab.size(0) < span:
+            raise ValueError(f"{op}: {name} holds {tab.size(0)} positions, the call reads up to position {span}")
+    if out is None:
+        out = torch.empty((T, 3 * HD), dtype=torch.bfloat16, device=dq.device)
+    _rows_arg(op, "out", out, T, 3 * HD)
+    if not out.is_contiguous():
+        raise ValueError(f"{op}: out must be dense, got strides {tuple(out.stride())}")
     if period:
-        if out is None:
-            out = torch.empty((T, 3 * HD), dtype=torch.bfloat16, device=dq.device)
-        _bf16(out)
-        assert out.shape == (T, 3 * HD) and out.is_contiguous() and T % period == 0
-        _launch("g4r_rope_qkv_bwd_batch_bf16", (_p(dq), _p(dk), _p(dv), _p(cos), _p(sin), _p(out), T, int(period), heads,
+        _launch("g4r_rope_qkv_bwd_batch_bf16", (_p(dq), _p(dk), _p(dv), _p(cos), _p(sin), _p(out), T, period, heads,
                                                 head_dim, pos0, dq.stride(0), dk.stride(0), dv.stride(0), _stream(dq),),
                 tag="g4r_rope_qkv_bwd_bf16")
         return out
-    if out is None:
-        out = torch.empty((T, 3 * HD), dtype=torch.bfloat16, device=dq.device)
-    _bf16(out)
-    assert out.shape == (T, 3 * HD) and out.is_contiguous()
     _launch("g4r_rope_qkv_bwd_bf16", (_p(dq), _p(dk), _p(dv), _p(cos), _p(sin), _p(out), T, heads, head_dim, pos0,
                                       dq.stride(0), dk.stride(0), dv.stride(0), _stream(dq),),
             tag="g4r_rope_qkv_bwd_bf16")
@@ -1257,14 +1312,24 @@ def rope_qkv_bwd(dq, dk, dv, cos, sin, heads, head_dim, pos0=0, out=None, period
 
 
 def cross_entropy(logits, labels, loss_sum, grad_scale=None, dlogits=None, n_pad=None):
-    """logits fp32 [R, N] (row-strided), labels int64 [R] (< 0 = ignored).  Adds the summed loss to loss_sum
-    (fp32 [1]); when dlogits (bf16 [R, >= n_pad]) is given it receives (softmax - onehot) * grad_scale[0]."""
+    """logits fp32 [R, N] (row-strided), labels int64 [R] (< 0 or >= N = ignored).  Adds the summed loss to loss_sum
+    (fp32 [1]); when dlogits (bf16 [R, >= n_pad], row-strided) is given it receives (softmax - onehot) * grad_scale[0]
+    in its first N columns and zeros up to n_pad (default: its width)."""
     _f32(logits, loss_sum, grad_scale)
+    op = "cross_entropy"
+    _rows_arg(op, "logits", logits)
     R, N = logits.shape
     assert labels.dtype == torch.int64 and labels.numel() == R and labels.is_contiguous()
+    _vec_arg(op, "loss_sum", loss_sum, 1)
+    _vec_arg(op, "grad_scale", grad_scale, 1)
     if dlogits is not None:
         _bf16(dlogits)
+        _rows_arg(op, "dlogits", dlogits, R)
         n_pad = n_pad or dlogits.size(1)
+        if grad_scale is None:
+            raise ValueError(f"{op}: dlogits needs grad_scale")
+        if not N <= n_pad <= dlogits.size(1):
+            raise ValueError(f"{op}: n_pad {n_pad} must lie between N = {N} and the width of dlogits, {dlogits.size(1)}")
     _launch("g4r_cross_entropy_f32", (_p(logits), _p(labels), _p(dlogits), _p(loss_sum), _p(grad_scale), R, N,
                                       logits.stride(0), dlogits.stride(0) if dlogits is not None else 0,
                                       n_pad or N, _stream(logits),), tag="g4r_cross_entropy_f32")
@@ -1272,30 +1337,41 @@ def cross_entropy(logits, labels, loss_sum, grad_scale=None, dlogits=None, n_pad
 
 
 def transpose(x, r_pad=None, out=None):
-    """x [R, C] bf16 (row-strided) -> [C, R_pad] with zero columns R..R_pad."""
-    _bf16(x)
+    """x [R, C] bf16 (row-strided) -> [C, R_pad] with zero columns R..R_pad (`out`: [C, >= R_pad], row-strided ok)."""
+    _bf16(x, out)
+    _rows_arg("transpose", "x", x)
     R, C = x.shape
     r_pad = r_pad or R
+    if r_pad < R:
+        raise ValueError(f"transpose: r_pad {r_pad} is below the {R} rows of x")
     if out is None:
         out = torch.empty((C, r_pad), dtype=torch.bfloat16, device=x.device)
+    _rows_arg("transpose", "out", out, C)
+    if out.size(1) < r_pad:
+        raise ValueError(f"transpose: out must be [{C}, >= {r_pad}], got shape {tuple(out.shape)}")
     _launch("g4r_transpose_bf16", (_p(x), _p(out), R, C, x.stride(0), out.stride(0), r_pad, _stream(x),),
             tag="g4r_transpose_bf16", nbytes=2.0 * (R * C + C * r_pad))
     return out
 
 
 def colsum(x, out=None):
+    """x [M, N] bf16 (row-strided) -> fp32 [N] column sums, ADDED to `out` when given."""
     _bf16(x)
+    _f32(out)
+    _rows_arg("colsum", "x", x)
     M, N = x.shape
+    _vec_arg("colsum", "out", out, N)
     if out is None:
         out = torch.zeros(N, dtype=torch.float32, device=x.device)
     _launch("g4r_colsum_bf16", (_p(x), _p(out), M, N, x.stride(0), _stream(x),), tag="g4r_colsum_bf16")
     return out
 
 
-def relu_bwd(y, dy):
-    _bf16(y, dy)
+def relu_bwd(y, dy, out=None):
+    _bf16(y, dy, out)
     assert y.is_contiguous() and dy.is_contiguous() and y.numel() == dy.numel()
-    dx = torch.empty_like(dy)
+    dx = torch.empty_like(dy) if out is None else out
+    assert dx.is_contiguous() and dx.numel() == dy.numel()
     _launch("g4r_relu_bwd_bf16", (_p(y), _p(dy), _p(dx), y.numel(), _stream(y),), tag="g4r_relu_bwd_bf16")
     return dx
 
@@ -1305,9 +1381,11 @@ def gather_rows(src, idx, out=None):
     copy: one kernel serves both storage types (the batched decode gathers its next embedding rows with it)."""
     dt = _h16(src, out)
     assert idx.dtype == torch.int32 and idx.is_contiguous()
+    _rows_arg("gather_rows", "src", src)
     n, C = idx.numel(), src.size(1)
     if out is None:
         out = torch.empty((n, C), dtype=dt, device=src.device)
+    _rows_arg("gather_rows", "out", out, n, C)
     _launch("g4r_gather_rows_bf16", (_p(src), _p(idx), _p(out), n, C, src.stride(0), out.stride(0), _stream(src),),
             tag="g4r_gather_rows_bf16")
     return out
