@@ -178,6 +178,65 @@ def plan_reuse(cached_ids, new_ids, same_image, cached_boxes, new_boxes, bbox_id
     return L
 
 
+def plan_shared_prefix(rows_ids, same_image, rows_boxes, bbox_id):
+    """How many leading positions the rows of ONE batch share: -> P, the batch is then prefilled once over [0, P) and the
+    rows decode against one copy of that prefix (LlamaDecoder.decode_graph_batch(shared_prefix=P)).  The sibling of
+    `plan_reuse`, across the rows of a batch instead of the turns of a conversation.
+
+    rows_ids: the real (unpadded) token ids of every row; same_image: every row's image equals row 0's; rows_boxes: per row,
+    the box of every `<bbox>` token (id `bbox_id`) in order of appearance, as 4-number sequences (or None).  P is
+      * the longest common prefix of all rows' ids;
+      * 0 if the images differ (every patch token's embedding depends on the image);
+      * cut to just before the first `<bbox>` position whose box differs, in any row, from row 0's box of the same ordinal
+        (that position's embedding is the box's feature);
+      * at most min_b n_b - 1: every row keeps at least one position of its own, so each has step-0 logits.
+    Pure host function."""
+    rows_ids = [list(r) for r in rows_ids]
+    if not rows_ids or not same_image or any(len(r) == 0 for r in rows_ids):
+        return 0
+    first = rows_ids[0]
+    P = min(len(r) for r in rows_ids) - 1
+    for r in rows_ids[1:]:
+        n = 0
+        while n < P and r[n] == first[n]:
+            n += 1
+        P = n
+    boxes = [[] if b is None else [[float(x) for x in box] for box in b] for b in (rows_boxes or [None] * len(rows_ids))]
+    if len(boxes) != len(rows_ids):
+        raise ValueError(f"{len(boxes)} box lists for {len(rows_ids)} rows")
+    k = 0
+    for p in range(P):
+        if first[p] != bbox_id:
+            continue
+        if not all(k < len(b) and b[k] == boxes[0][k] for b in boxes):
+            return p
+        k += 1
+    return P
+
+
+def right_padded_lengths(attention_mask, B, T):
+    """The rows' real lengths of a RIGHT-padded [B, T] mask (None: all T) as a list of ints; ValueError for any other mask
+    (left padding, holes, an empty row).  One small device->host read."""
+    if attention_mask is None:
+        return [int(T)] * int(B)
+    if attention_mask.dim() != 2 or tuple(attention_mask.shape) != (B, T):
+        raise ValueError(f"attention_mask must be [{B}, {T}], got {tuple(attention_mask.shape)}")
+    rows = attention_mask.to(torch.bool).cpu().tolist()
+    lens = [sum(r) for r in rows]
+    if any(n == 0 or not all(r[:n]) for r, n in zip(rows, lens)):
+        raise ValueError("shared_prefix needs a RIGHT-padded batch: each row's real tokens first, then the padding")
+    return lens
+
+
+def _batch_box_rows(bboxes, B):
+    """The boxes of a batch as B lists of 4-float lists (bboxes: None, or the reference's list of B [n_b, 4] tensors)."""
+    if bboxes is None:
+        return [[] for _ in range(B)]
+    if hasattr(bboxes, "boxes_h16") or len(bboxes) != B:
+        raise ValueError(f"shared_prefix reads the boxes as a list of {B} [n, 4] tensors, one per row")
+    return [[[float(x) for x in row] for row in b.detach().float().cpu().tolist()] for b in bboxes]
+
+
 def _box_rows(bboxes):
     """The boxes of a batch-1 request as a list of 4-float lists (bboxes: None, or the reference's list of one [n, 4])."""
     if bboxes is None:

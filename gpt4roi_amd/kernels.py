@@ -31,6 +31,8 @@ _SIGS = {
                              c_int, c_long, c_long, c_long, c_long, P],
     "g4r_attn_decode_ragged_bf16": [P, P, P, P, P, P, P, P, c_int, c_int, c_long, c_long, c_float, c_int, P, P, c_int,
                                     c_long, c_long, c_long, c_long, P],
+    "g4r_attn_decode_shared_bf16": [P, P, P, P, P, P, P, c_long, P, c_long, c_int, c_int, c_long, c_long, c_float, c_int, P,
+                                    P, c_int, c_long, c_long, c_long, c_long, c_int, c_int, c_int, c_int, P],
     "g4r_batch_advance_ragged": [P, c_int, P, P, P, P, P, c_int, c_int, P],
     "g4r_gemv_attn_merge_bf16": [P, c_int, c_int, P, P, P, P, c_int, c_int, c_int, c_int, P],
     "g4r_flash_attn_bwd_bf16": [P] * 10 + [c_int] * 5 + [c_long] * 16 + [c_float, c_int, P],
@@ -814,6 +816,73 @@ def attn_decode(q, k, v, heads, scale, work, kv_len_dev=None, kv_len=None, out=N
                                      _p(kv_len_dev), int(bool(defer_merge)), B, src.numel() // B,
                                      k.stride(0) if batched else 0, v.stride(0) if batched else 0, HD, _stream(k),),
             tag=f"attn_decode<{D}>", dt=dt)
+    return out
+
+
+SHARED_ATTN_ROWS = 16       # sequences one workgroup of g4r_attn_decode_shared_bf16 serves (one MFMA operand)
+SHARED_ATTN_ROUTE = "rule"  # "rule" = shared_attn_wins below; "always" / "never" pin a route (tools, tests)
+
+
+def shared_attn_wins(B, P, heads, head_dim=128):
+    """Routing rule of the decode attention of a shared-prefix batch (LlamaDecoder.decode_graph_batch(shared_prefix=P)):
+    whether a step runs on attn_decode_shared (prefix K/V fetched once per group of 16 rows, MFMA) instead of the per-row
+    ragged attn_decode.  The kernel is routed only where a hipGraph-timed A/B of the launch shows a win beyond the spread of
+    the repeats at that point (tools/shared_prefix_ab.py, profiles/shared_prefix_ab.txt: H = 32, D = 128, B 2-32 x P 64-1500,
+    167 own keys).  It wins at every measured point with P >= 600 and B >= 4 (1.1-3.2x) and at B = 32 / P = 256 (1.02x), and
+    at none of the others (its own-key phase costs more than the prefix saves below that), so those two lines are the rule,
+    for the measured head count and head_dim only; the existing kernel runs everywhere else."""
+    applies = B >= 1 and P >= 0 and head_dim in (64, 128)
+    if SHARED_ATTN_ROUTE != "rule":
+        return applies and SHARED_ATTN_ROUTE == "always"
+    return applies and heads == 32 and head_dim == 128 and ((B >= 4 and P >= 600) or (B >= 32 and P >= 256))
+
+
+def shared_attn_splits(heads, batch):
+    """Key splits of attn_decode_shared: enough workgroups (splits x heads x row groups) for the 256 CUs, 8 at the most."""
+    return max(1, min(8, 512 // max(1, heads * -(-batch // SHARED_ATTN_ROWS))))
+
+
+class SharedAttnWorkspace:
+    """Partials + arrival counters of attn_decode_shared for up to `batch` sequences: [batch, heads, splits, D + 2] fp32 and
+    one counter per (row group of 16, head).  Sized up front (captured graphs hold its addresses); a call leaves the counters
+    zero and nothing in the partials that a later call reads."""
+
+    def __init__(self, heads, head_dim, device, splits=8, batch=1):
+        self.heads, self.head_dim, self.splits, self.batch = heads, head_dim, splits, batch
+        self.ws = torch.empty(batch * heads * splits * (head_dim + 2), dtype=torch.float32, device=device)
+        self.cnt = torch.zeros(-(-batch // SHARED_ATTN_ROWS) * heads, dtype=torch.int32, device=device)
+
+
+def attn_decode_shared(qkv, k, v, heads, scale, work, cos, sin, kv_lens_dev, prefix_len_dev, out=None, splits=None,
+                       prefix_len=None, kv_lens=None):
+    """One decode step of B sequences whose first P = prefix_len_dev[0] cache rows hold the same tokens
+    (csrc/attention_shared.hip).  qkv [B, 3*heads*D] raw projection rows, k/v [B, T_max, heads*D] cache views, kv_lens_dev
+    int32 [B], prefix_len_dev int32 [1] -> out [B, heads*D].  Sequence b attends rows [0, P) of slot 0, rows
+    [P, kv_lens_dev[b]) of slot b and its new key; RoPE at position kv_lens_dev[b], append at that row of slot b (the same
+    bits as attn_decode(kv_lens_dev=..., rope_pos_dev=None)).  0 <= P <= min(kv_lens).  work: a SharedAttnWorkspace;
+    splits: key splits (default work.splits).  prefix_len / kv_lens: the host's copies where it has them -- a prefix
+    longer than a sequence, or a length beyond the cache, is then refused before the launch."""
+    dt = _h16(k, v, qkv)
+    assert k.dim() == 3 and v.shape == k.shape and k.stride(-1) == 1 and v.stride(-1) == 1
+    B, Tmax, HD = k.shape
+    D = HD // heads
+    assert qkv.dim() == 2 and qkv.size(0) == B and qkv.size(1) == 3 * HD and qkv.stride(1) == 1
+    _f32(cos, sin, work.ws)
+    assert cos.size(1) == D // 2 and cos.is_contiguous() and sin.shape == cos.shape and sin.is_contiguous()
+    assert kv_lens_dev.dtype == torch.int32 and kv_lens_dev.numel() >= B and kv_lens_dev.is_contiguous()
+    assert prefix_len_dev.dtype == torch.int32 and prefix_len_dev.numel() >= 1
+    _lib.require_gpu(kv_lens_dev, prefix_len_dev, work.cnt)
+    if out is None:
+        out = torch.empty((B, HD), dtype=dt, device=k.device)
+    assert out.dtype == dt and out.numel() == B * HD and out.is_contiguous()
+    S = int(splits) if splits else work.splits
+    lens = [int(x) for x in kv_lens] if kv_lens is not None else None
+    _launch("g4r_attn_decode_shared_bf16", (
+        _p(qkv), _p(cos), _p(sin), _p(k), _p(v), _p(out), _p(work.ws), work.ws.numel(), _p(work.cnt), work.cnt.numel(),
+        heads, D, k.stride(1), v.stride(1), float(scale), S, _p(kv_lens_dev), _p(prefix_len_dev), B, qkv.stride(0),
+        k.stride(0), v.stride(0), HD, min(Tmax, cos.size(0)), -1 if prefix_len is None else int(prefix_len),
+        min(lens) if lens else -1, max(lens) if lens else -1, _stream(k),),
+        tag=f"attn_decode_shared<{D}>", dt=dt)
     return out
 
 

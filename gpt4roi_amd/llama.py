@@ -527,6 +527,54 @@ class LlamaDecoder:
                 pool[batch] = K.DecodeAttnWorkspace(self.heads, self.head_dim, self.device, splits=splits, batch=batch)
         return pool[batch]
 
+    def _shared_attn_work(self, batch):
+        """Workspace of the shared-prefix decode attention (kernels.attn_decode_shared); one per batch size, sized up front and
+        never freed (captured decode graphs hold its addresses)."""
+        pool = getattr(self, "_shared_ws", None)
+        if pool is None:
+            pool = self._shared_ws = {}
+        if batch not in pool:
+            with torch.inference_mode(False):
+                pool[batch] = K.SharedAttnWorkspace(self.heads, self.head_dim, self.device,
+                                                    splits=K.shared_attn_splits(self.heads, batch), batch=batch)
+        return pool[batch]
+
+    def _prefill_shared(self, inputs_embeds, key_padding_mask, P, max_new_tokens):
+        """Prefill of decode_graph_batch(shared_prefix=P): -> (step-0 logits [B, V], the rows' lengths n_b).  Existing
+        kernels only: the prefix once at batch 1 into slot 0, its K/V rows copied to the other slots (so the per-row ragged
+        kernel stays usable on the same cache), then the B right-padded suffix blocks through the dense forward at position
+        P -- right padding is invisible to the real rows under the causal mask (generation.dense_or_mask)."""
+        if inputs_embeds.dim() != 3:
+            raise ValueError("shared_prefix: inputs_embeds must be [B, T, C]")
+        B, T, C = inputs_embeds.shape
+        P = int(P)
+        if key_padding_mask is None:
+            lens = [T] * B
+        else:
+            m = key_padding_mask.to(torch.bool)
+            if m.shape != (B, T):
+                raise ValueError(f"shared_prefix: key_padding_mask must be [{B}, {T}], got {tuple(m.shape)}")
+            lens = [int(x) for x in m.sum(1).tolist()]
+            want = torch.arange(T, device=m.device)[None, :] < torch.tensor(lens, device=m.device)[:, None]
+            if not bool(torch.equal(m, want)):
+                raise ValueError("shared_prefix: the batch must be RIGHT-padded (each row's real tokens first)")
+        if P < 0 or not all(P < n <= T for n in lens):
+            raise ValueError(f"shared_prefix = {P}: every row needs P < n_b <= T = {T} real tokens, got {lens}")
+        if max(lens) + max_new_tokens > self.max_positions:
+            raise ValueError(f"shared_prefix: {max(lens)} prompt positions + {max_new_tokens} new tokens exceed the "
+                             f"{self.max_positions} cache rows")
+        self.reset(B)
+        if P > 0:
+            self.forward(inputs_embeds[:1, :P], return_hidden=True)          # slot 0, positions [0, P)
+            self.kc[:, 1:B, :P].copy_(self.kc[:, :1, :P].expand(-1, B - 1, -1, -1))
+            self.vc[:, 1:B, :P].copy_(self.vc[:, :1, :P].expand(-1, B - 1, -1, -1))
+        xn = self.forward(inputs_embeds[:, P:], return_hidden=True)          # [B, T - P, C] at positions P ..
+        last = torch.tensor([b * (T - P) + n - 1 - P for b, n in enumerate(lens)], dtype=torch.int32, device=xn.device)
+        rows = K.gather_rows(xn.reshape(B * (T - P), C), last)
+        logits = K.gemm(rows, self.lm_head, out_dtype=torch.float32)
+        self.rows_held = 0
+        return logits.view(B, self.vocab), lens
+
     def _advance(self, logits_row, st, sampler):
         """Token selection on the device: argmax (generate(do_sample=False)) or one temperature / top-k / top-p draw
         (do_sample=True, app.py:293-300); sampler = (temperature, top_k, top_p)."""
@@ -664,7 +712,14 @@ class LlamaDecoder:
         nl = len(self.layers)
         for li, L in enumerate(self.layers):
             qkv = norm_proj(x, L['n1'], L['wqkv'], h=h)
-            if st.get("ragged"):            # pos = [B cache lengths | RoPE position], all advanced by batch_advance
+            if st.get("shared"):            # pos = the B cache lengths = the rows' own RoPE positions; plen = the shared prefix
+                if st["route"]:
+                    a = K.attn_decode_shared(qkv, self.kc[li, :B], self.vc[li, :B], H, scale, self._shared_attn_work(B),
+                                             self.cos, self.sin, st["pos"], st["plen"])
+                else:
+                    a = K.attn_decode(None, self.kc[li, :B], self.vc[li, :B], H, scale, work, qkv=qkv, cos=self.cos,
+                                      sin=self.sin, kv_lens_dev=st["pos"], rope_pos_dev=None)
+            elif st.get("ragged"):          # pos = [B cache lengths | RoPE position], all advanced by batch_advance
                 a = K.attn_decode(None, self.kc[li, :B], self.vc[li, :B], H, scale, work, qkv=qkv, cos=self.cos,
                                   sin=self.sin, kv_lens_dev=st["pos"][:B], rope_pos_dev=st["pos"][B:])
             else:
@@ -688,7 +743,8 @@ class LlamaDecoder:
 
     @torch.no_grad()
     def decode_graph_batch(self, inputs_embeds, max_new_tokens, stop_ids=(), use_graph=True, key_padding_mask=None,
-                           sampler=None, seeds=None, on_tokens=None, check_every=None):
+                           sampler=None, seeds=None, on_tokens=None, check_every=None, shared_prefix=None,
+                           own_positions=None):
         """generate() for B sequences, per-token loop on the device.  Prompts of equal length, or -- with
         key_padding_mask (bool [B, T]) -- prompts padded to a common T on either side (HF batch generation pads on the
         left; merged serving requests of different lengths pad on the right): see `forward`.  Prefill
@@ -706,16 +762,41 @@ class LlamaDecoder:
         Sampled, or with on_tokens(b, ids of row b so far) -> bool: every `check_every` steps (default 32) the host reads
         the new ids; row b is finished at its first stop id or the first prefix on_tokens accepts (each prefix is shown
         once), the loop ends when every row has finished, and each row is cut at its own end (inclusive); self.pos then
-        counts the steps actually run."""
+        counts the steps actually run.
+
+        shared_prefix = P >= 1 (default None / 0: everything above): the first P positions of every row are the same
+        tokens -- one image and many questions, n samples of one prompt.  inputs_embeds [B, T, C], key_padding_mask None or
+        RIGHT-padded, row b with n_b real tokens, P < n_b <= T; anything else raises ValueError before the cache is
+        touched.  Positions [0, P) are taken from row 0 only: the caller guarantees that the rows agree there.  The prefix
+        is prefilled ONCE (batch 1, slot 0) and its K/V rows are copied to the other slots; only the suffixes run at batch
+        B.  Positions: every row is computed at its OWN positions, 0 .. n_b - 1 for the prompt and n_b + s for step s --
+        what the row gets when it is served alone.  The masked batch above instead keeps the positions of the PADDED
+        layout (one RoPE position per step for all rows), so a right-padded batch gives different logits on the two paths
+        unless all rows have one length.  Each decode step attends with kernels.attn_decode_shared (prefix K/V read once
+        per group of 16 rows) where kernels.shared_attn_wins(B, P, heads, head_dim) says so, else with the ragged
+        attn_decode at rope_pos_dev=None; the captured graph is kept per (B, route) and serves any P (P lives in device
+        memory).  own_positions=True takes this path with P = 0 (an empty prefix).  Sampling, seeds, on_tokens, stopping
+        and the pos / rows_held = 0 / cache_version contracts are those of the masked batch."""
         from .generation import expand_seeds, row_samplers
         B = inputs_embeds.size(0)
+        P = int(shared_prefix or 0)
+        shared = bool(own_positions) if own_positions is not None else P >= 1
+        if P >= 1 and not shared:
+            raise ValueError("shared_prefix >= 1 runs at the rows' own positions: own_positions=False contradicts it")
         rows = row_samplers(sampler, B)
         sampled = any(r is not None for r in rows)
         early = sampled or on_tokens is not None
         every = max(1, int(check_every)) if check_every is not None else 32
-        self.reset(B)
-        logits = self.forward(inputs_embeds, all_logits=False, key_padding_mask=key_padding_mask)
-        T = self.pos
+        lens = route = None
+        if shared:
+            logits, lens = self._prefill_shared(inputs_embeds, key_padding_mask, P, max_new_tokens)
+            self.shared_step0_logits = logits                           # [B, V] fp32, for tools and tests
+            T = max(lens)
+            route = bool(K.shared_attn_wins(B, P, self.heads, self.head_dim))
+        else:
+            self.reset(B)
+            logits = self.forward(inputs_embeds, all_logits=False, key_padding_mask=key_padding_mask)
+            T = self.pos
         assert T + max_new_tokens <= self.max_positions
         dev = inputs_embeds.device
         ragged = self.ragged is not None
@@ -723,6 +804,8 @@ class LlamaDecoder:
         if pool is None:
             pool = self._bstate = {}
         key = (B, ragged, True) if sampled else (B, ragged)             # the greedy state keeps its key and its graph
+        if shared:
+            key = (B, "shared", route, sampled)                         # the mode and the attention route pick the graph
         bs = pool.get(key)
         if bs is None or bs["out"].size(1) < max_new_tokens:
             cap = max(64, 1 << (max_new_tokens - 1).bit_length())      # output slots: the captured graph knows this stride
@@ -730,8 +813,11 @@ class LlamaDecoder:
                 bs = pool[key] = dict(B=B, ragged=ragged, tok=torch.zeros(B, dtype=torch.int64, device=dev),
                                       tok32=torch.zeros(B, dtype=torch.int32, device=dev),
                                       out=torch.zeros((B, cap), dtype=torch.int64, device=dev),
-                                      pos=torch.zeros(B + 1 if ragged else 1, dtype=torch.int32, device=dev),
+                                      pos=torch.zeros(B if shared else (B + 1 if ragged else 1), dtype=torch.int32,
+                                                      device=dev),
                                       step=torch.zeros(1, dtype=torch.int32, device=dev), graph=None)
+                if shared:
+                    bs.update(shared=True, route=route, plen=torch.zeros(1, dtype=torch.int32, device=dev))
                 if sampled:
                     bs.update(sampled=True, temp=torch.zeros(B, dtype=torch.float32, device=dev),
                               topk=torch.zeros(B, dtype=torch.int32, device=dev),
@@ -746,7 +832,10 @@ class LlamaDecoder:
             st["topp"].copy_(torch.tensor([r[2] if r else 1.0 for r in rows], dtype=torch.float32))
             st["seed"].copy_(torch.tensor([x - 2 ** 64 if x >= 2 ** 63 else x for x in seeds], dtype=torch.int64))
             st["u"].zero_()
-        if ragged:
+        if shared:
+            st["pos"].copy_(torch.tensor([n - 1 for n in lens], dtype=torch.int32))   # the advance below moves them on
+            st["plen"].fill_(P)
+        elif ragged:
             st["pos"].copy_(self._rag_pos - 1)                          # [n_b - 1 ..., T - 1]: the advance below moves them on
         else:
             st["pos"].fill_(T - 1)

@@ -179,11 +179,14 @@ class ConversationBot:
         history_cache[-1]['sources']['conversations'].append({'from': 'gpt', 'value': answer})
         return shown, None, history_cache
 
-    def batch_inputs(self, texts, images, history_caches):
+    def batch_inputs(self, texts, images, history_caches, pad_side="left"):
         """check_input + init_inputs for each conversation, then the batch: prompts LEFT-padded with the tokenizer's pad id
-        (HF batch generation style) -> (results, rows, dict(input_ids [B, T], attention_mask [B, T], images [B, 3, S, S],
-        bboxes list of B)).  results[i] is (None, error, history_caches[i]) for a conversation that fails its check, else
-        None; rows lists the conversations in the batch, in order."""
+        (HF batch generation style; pad_side="right": right-padded, what generate(shared_prefix=True) takes) -> (results,
+        rows, dict(input_ids [B, T], attention_mask [B, T], images [B, 3, S, S], bboxes list of B)).  results[i] is
+        (None, error, history_caches[i]) for a conversation that fails its check, else None; rows lists the conversations
+        in the batch, in order."""
+        if pad_side not in ("left", "right"):
+            raise ValueError(f"pad_side = {pad_side!r}: 'left' or 'right'")
         results, rows, ids, imgs, boxes = [None] * len(texts), [], [], [], []
         for i, (text, image, hist) in enumerate(zip(texts, images, history_caches)):
             error, text = self.check_input(text, image, hist)
@@ -204,13 +207,15 @@ class ConversationBot:
         input_ids = torch.full((len(rows), T), pad, dtype=torch.int64)
         mask = torch.zeros((len(rows), T), dtype=torch.int64)
         for r, x in enumerate(ids):
-            input_ids[r, T - x.numel():] = x
-            mask[r, T - x.numel():] = 1
+            lo = T - x.numel() if pad_side == "left" else 0
+            input_ids[r, lo:lo + x.numel()] = x
+            mask[r, lo:lo + x.numel()] = 1
         batch = dict(input_ids=input_ids.to(self.device), attention_mask=mask.to(self.device),
                      images=torch.stack([im.to(self.device) for im in imgs], 0), bboxes=boxes)
         return results, rows, batch
 
-    def run_batch(self, texts, images, history_caches, do_sample=True, temperature=0.2, max_new_tokens=1024, seeds=None):
+    def run_batch(self, texts, images, history_caches, do_sample=True, temperature=0.2, max_new_tokens=1024, seeds=None,
+                  share_prefix=False):
         """Several conversations, one question each, answered by ONE batched generate(): -> list of
         (answer or None, error or None, history_cache), one per conversation.  Each conversation is checked and assembled
         as `run` does it; those that fail the check return their error and stay out of the batch.  The prompts are
@@ -218,8 +223,12 @@ class ConversationBot:
         with its own Philox stream and stopped by the '###' criterion on its own ids; the answers are cleaned up and
         appended to each history exactly as `run` does.  seeds: None (drawn), an int (expanded over the batch rows, see
         generate) or a list with one seed per conversation (a conversation then draws what `run(seed=...)` would draw on
-        the same logits).  `run` stays the batch-1 path."""
-        results, rows, batch = self.batch_inputs(texts, images, history_caches)
+        the same logits).  `run` stays the batch-1 path.
+        share_prefix: the batch is built RIGHT-padded and generated with shared_prefix=True -- several questions about one
+        image share the system header and the image tokens, which are then prefilled once and read once per decode step
+        for the whole batch; every conversation is computed at its own positions, as `run` computes it.  Conversations
+        about different images share nothing (P = 0) and still decode together.  Answers and histories as above."""
+        results, rows, batch = self.batch_inputs(texts, images, history_caches, pad_side="right" if share_prefix else "left")
         if not rows:
             return results
         if isinstance(seeds, (list, tuple)):
@@ -239,7 +248,7 @@ class ConversationBot:
                 new = model.generate(input_ids, images=batch['images'], attention_mask=batch['attention_mask'],
                                      do_sample=do_sample, temperature=temperature, max_new_tokens=max_new_tokens,
                                      stopping_criteria=[criteria], seed=seeds, pad_token_id=self.tokenizer.pad_token_id,
-                                     return_new_tokens=True)
+                                     return_new_tokens=True, **(dict(shared_prefix=True) if share_prefix and len(rows) > 1 else {}))
             finally:
                 model.forward = model.orig_forward
         if len(rows) == 1:

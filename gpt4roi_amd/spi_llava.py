@@ -39,7 +39,8 @@ import torch.nn as nn
 
 from . import kernels as K
 from .generation import (GenerationSession, KeywordsStoppingCriteria, SamplingConfig,  # noqa: F401 (re-exported)
-                         StoppingCriteria, _box_rows, dense_or_mask, expand_seeds, prepare_inputs_for_generation)
+                         StoppingCriteria, _batch_box_rows, _box_rows, dense_or_mask, expand_seeds, plan_shared_prefix,
+                         prepare_inputs_for_generation, right_padded_lengths)
 from .layers import MLVLROIQueryModule, PreparedBoxes
 from .llama import LlamaDecoder
 from .vit import ClipVisionTower
@@ -611,7 +612,8 @@ class SPILlavaMPTForCausalLM(nn.Module):
     @torch.no_grad()
     def generate(self, input_ids=None, images=None, max_new_tokens=64, do_sample=None, temperature=None, top_k=None,
                  top_p=None, stopping_criteria=None, eos_token_id=None, seed=None, bboxes=None, stop_ids=(),
-                 check_every=None, return_new_tokens=False, attention_mask=None, pad_token_id=None, session=None, **_):
+                 check_every=None, return_new_tokens=False, attention_mask=None, pad_token_id=None, session=None,
+                 shared_prefix=None, num_return_sequences=None, **_):
         """HF-style `generate`.  Batch 1 (what gpt4roi/app.py:293-300 calls): prefill through `self.forward` -- so a
         `partial(orig_forward, img_metas=..., bboxes=...)` bound by the caller is honoured (app.py:286-291; `bboxes=`
         may also be passed here) -- then the device-resident decode loop.  do_sample=False: greedy (the parity mode);
@@ -633,14 +635,46 @@ class SPILlavaMPTForCausalLM(nn.Module):
         session (batch 1 only): a generation.GenerationSession kept by the caller for one conversation.  The vision path
         and the splice run as always; then only the prompt positions behind the longest cache prefix the session may
         trust (generation.plan_reuse: same ids, same image, same boxes) are prefilled, and the session is updated with
-        what the cache holds afterwards.  Sampling, seeds, stopping and the return value are those of a call without it."""
+        what the cache holds afterwards.  Sampling, seeds, stopping and the return value are those of a call without it.
+        shared_prefix (B > 1): None = the masked batch above.  True: the rows are RIGHT-padded and share a prompt prefix
+        -- P = generation.plan_shared_prefix (same ids, images `torch.equal` to row 0's, same boxes; possibly 0) is
+        prefilled once, every row runs at its OWN positions (as if served alone, not the padded layout's) and each decode
+        step reads the prefix K/V once for the batch (LlamaDecoder.decode_graph_batch(shared_prefix=P)).  An int is
+        checked against that plan and must not exceed it.  A mask that is not right-padded, or an int beyond the plan,
+        raises ValueError before the model is touched.
+        num_return_sequences = n > 1 (batch 1, do_sample=True): n samples of the ONE prompt through the shared path with
+        P = T - 1; `seed` expands over the n rows like a batch's (generation.expand_seeds).  Returns [n, T + longest] padded
+        with pad_token_id (or a list of n id lists with return_new_tokens).  ValueError with greedy decoding (n equal rows,
+        as in HF), with B > 1 and with session=.  The vision path still runs per row."""
+        n_ret = 1 if num_return_sequences is None else int(num_return_sequences)
+        if n_ret < 1:
+            raise ValueError(f"num_return_sequences = {num_return_sequences}: has to be >= 1")
+        if n_ret > 1:
+            if input_ids.size(0) > 1:
+                raise ValueError("num_return_sequences > 1 takes ONE prompt; got a batch of "
+                                 f"{input_ids.size(0)} (repeat the rows and pass shared_prefix=True instead)")
+            if session is not None:
+                raise ValueError("num_return_sequences > 1 cannot continue a session (a session holds ONE conversation)")
+            sampling = self.generation_config.do_sample if do_sample is None else bool(do_sample)
+            if not sampling:
+                raise ValueError("num_return_sequences > 1 needs do_sample=True: greedy decoding would return "
+                                 f"{n_ret} equal sequences")
+            if shared_prefix not in (None, True):
+                raise ValueError("num_return_sequences > 1 shares the whole prompt; shared_prefix= is not taken with it")
+            if input_ids.size(1) < 2:
+                raise ValueError("num_return_sequences > 1 needs a prompt of at least 2 tokens")
+            return self._generate_batch(input_ids, images, max_new_tokens, do_sample, temperature, top_k, top_p, seed,
+                                        stopping_criteria, eos_token_id, bboxes, stop_ids, check_every, return_new_tokens,
+                                        attention_mask, pad_token_id, copies=n_ret)
+        if shared_prefix is not None and shared_prefix is not False and input_ids.size(0) == 1:
+            raise ValueError("shared_prefix= is for a batch (B > 1); one prompt with n samples: num_return_sequences=n")
         if session is not None and input_ids.size(0) > 1:
             raise ValueError(f"generate(session=...) continues ONE conversation; got a batch of {input_ids.size(0)} sequences "
                              "(batched and ragged continuation is not supported: call without a session)")
         if input_ids.size(0) > 1:
             return self._generate_batch(input_ids, images, max_new_tokens, do_sample, temperature, top_k, top_p, seed,
                                         stopping_criteria, eos_token_id, bboxes, stop_ids, check_every, return_new_tokens,
-                                        attention_mask, pad_token_id)
+                                        attention_mask, pad_token_id, shared_prefix=shared_prefix)
         if isinstance(seed, (list, tuple)):
             if len(seed) != 1:
                 raise ValueError(f"{len(seed)} seeds for a batch of 1 sequence")
@@ -692,8 +726,21 @@ class SPILlavaMPTForCausalLM(nn.Module):
 
     def _generate_batch(self, input_ids, images, max_new_tokens, do_sample, temperature, top_k, top_p, seed,
                         stopping_criteria, eos_token_id, bboxes, stop_ids, check_every, return_new_tokens, attention_mask,
-                        pad_token_id):
-        B = input_ids.size(0)
+                        pad_token_id, shared_prefix=None, copies=1):
+        """copies = n > 1: the ONE prompt row is served n times through the shared-prefix path (num_return_sequences)."""
+        B = input_ids.size(0) if copies == 1 else copies
+        if shared_prefix is False:
+            shared_prefix = None
+        lens = None
+        if copies > 1:
+            lens = right_padded_lengths(attention_mask, 1, input_ids.size(1)) * copies
+            if lens[0] != input_ids.size(1):
+                raise ValueError("num_return_sequences > 1 takes an unpadded prompt")
+        elif shared_prefix is not None:
+            if shared_prefix is not True and (isinstance(shared_prefix, bool) or not isinstance(shared_prefix, int)
+                                              or shared_prefix < 0):
+                raise ValueError(f"shared_prefix = {shared_prefix!r}: None, True or an int >= 0")
+            lens = right_padded_lengths(attention_mask, B, input_ids.size(1))
         gc = self.generation_config
         cfg = SamplingConfig(do_sample=gc.do_sample if do_sample is None else bool(do_sample),
                              temperature=gc.temperature if temperature is None else temperature,
@@ -701,7 +748,29 @@ class SPILlavaMPTForCausalLM(nn.Module):
         sampler = cfg.sampler()
         seeds = expand_seeds(seed, B) if sampler is not None else None      # (validates a list's length before any work)
         kw = dict(bboxes=bboxes) if bboxes is not None else {}
+        P = None
+        if copies > 1:
+            P = input_ids.size(1) - 1                       # n rows of one prompt: everything but the last position
+        elif shared_prefix is not None:
+            bound = getattr(self.forward, "keywords", None) or {}
+            boxes = _batch_box_rows(kw.get("bboxes", bound.get("bboxes")), B)
+            same = images is None or all(bool(torch.equal(images[b], images[0])) for b in range(1, B))
+            ids = input_ids.tolist()
+            bbox_id = getattr(getattr(getattr(self, "model", None), "config", None), "bbox_token", None)
+            plan = plan_shared_prefix([ids[b][:lens[b]] for b in range(B)], same, boxes, bbox_id)
+            if shared_prefix is True:
+                P = plan
+            elif shared_prefix > plan:
+                raise ValueError(f"shared_prefix = {shared_prefix}: the rows share only {plan} positions "
+                                 "(generation.plan_shared_prefix)")
+            else:
+                P = int(shared_prefix)
+        self.last_shared_prefix = P                         # what the last batched call planned (None: the masked batch)
         embeds = self._prefill_embeds(self.forward, self.prepare_inputs_for_generation(input_ids, images=images), kw)
+        if copies > 1:
+            embeds = embeds.expand(copies, -1, -1)
+            input_ids = input_ids.expand(copies, -1)
+            attention_mask = None
         stops = set(int(s) for s in stop_ids)
         if eos_token_id is None:
             eos_token_id = getattr(self.config, "eos_token_id", None)
@@ -718,7 +787,8 @@ class SPILlavaMPTForCausalLM(nn.Module):
                 return any(bool(c(seq, None)) for c in stopping_criteria)
         every = check_every if check_every is not None else (1 if stopping_criteria else 32)
         new = self.model.llama.decode_graph_batch(embeds, max_new_tokens, stop_ids=stops, key_padding_mask=attention_mask,
-                                                  sampler=sampler, seeds=seeds, on_tokens=on_tokens, check_every=every)
+                                                  sampler=sampler, seeds=seeds, on_tokens=on_tokens, check_every=every,
+                                                  shared_prefix=P, own_positions=None if P is None else True)
         if return_new_tokens:
             return new
         pad = pad_token_id if pad_token_id is not None else (getattr(self.config, "pad_token_id", None) or 0)

@@ -158,6 +158,26 @@ int g4r_attn_decode_ragged_bf16(const void* qkv, const float* cos_tab, const flo
                                 long q_batch, long k_batch, long v_batch, long o_batch, void* stream);
 
 /*
+ * The same step for a batch whose first *prefix_len_dev cache rows hold the SAME tokens in every sequence (one image, many
+ * questions; n samples of one prompt): sequence b attends rows [0, P) of cache slot 0, rows [P, kv_lens_dev[b]) of its own
+ * slot and its new key, RoPE at position kv_lens_dev[b], append at that row of slot b -- the appended rows are bit-equal
+ * to g4r_attn_decode_ragged_bf16's with a null rope_pos_dev.  The prefix K/V is fetched once per (head, key split) for a
+ * group of up to 16 sequences and multiplied on the matrix pipe (gpt4roi_amd/csrc/attention_shared.hip).  P lives in device
+ * memory like the lengths: 0 <= P <= min_b kv_lens_dev[b]; P = 0 is per-row attention.  For a fixed `splits` (1..32) the
+ * output row of a sequence does not depend on the other sequences of the launch or on its index among them.
+ * workspace: >= batch*H*splits*(head_dim+2) floats; counters: >= ceil(batch/16)*H uint32, zero before the first call, left
+ * zero by every call; `t_max` = rows per cache slot (and at most the rows of cos/sin): device lengths are clamped below it.
+ * prefix_len_host / min_len_host / max_len_host: what the host knows of P and the lengths (negative = unknown); a prefix
+ * longer than a sequence and lengths beyond t_max are refused with G4R_ERR_INVALID_ARG.
+ */
+int g4r_attn_decode_shared_bf16(const void* qkv, const float* cos_tab, const float* sin_tab, void* K, void* V, void* O,
+                                float* workspace, long workspace_floats, unsigned* counters, long counters_len, int H,
+                                int head_dim, long k_row, long v_row, float scale, int splits, const int* kv_lens_dev,
+                                const int* prefix_len_dev, int batch, long q_batch, long k_batch, long v_batch,
+                                long o_batch, int t_max, int prefix_len_host, int min_len_host, int max_len_host,
+                                void* stream);
+
+/*
  * o_proj of the decode step with the merge of the attention partials fused into its input staging:
  * C [N] = W [N, K] . a + bias + residual, a [K = H*head_dim] = the attention output assembled from
  * `partials` [H][splits][head_dim + 2] fp32 as written by g4r_attn_decode_bf16(..., defer_merge = 1).  Bit-identical to
