@@ -45,6 +45,7 @@ import torch.nn.functional as F
 from oracle.transformer_oracle import apply_rope, rope_tables
 
 U_BF16, U_F32 = 2.0 ** -8, 2.0 ** -24
+U_F16 = 2.0 ** -11                # (tests/_region_ref.py: the forward region kernels also run in fp16)
 R = 2.0 ** -22
 FLOOR = 2.0 ** -118
 E = 1.0                          # measured 0.996 (module docstring); rounded up
@@ -142,7 +143,7 @@ def colsum_case(M, N, seed=0):
 # ---- the measure -----------------------------------------------------------------------------------------------------
 def error(got, ref, cond, r=R):
     """Elementwise |got - ref| / (u_out |ref| + r cond + FLOOR), u_out from the dtype of `got`; non-finite -> inf."""
-    u = {torch.bfloat16: U_BF16, torch.float32: U_F32}[got.dtype]
+    u = {torch.bfloat16: U_BF16, torch.float32: U_F32, torch.float16: U_F16}[got.dtype]
     ref = ref.to(got.device)
     e = (got.detach().double() - ref).abs() / (u * ref.abs() + r * cond.to(got.device) + FLOOR)
     return torch.where(torch.isfinite(e), e, torch.full_like(e, float("inf")))
