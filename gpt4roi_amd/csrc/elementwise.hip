@@ -383,23 +383,15 @@ __global__ __launch_bounds__(256) void swiglu_kernel(const h16_t* __restrict__ g
 // grid = (token chunks, samples): every workgroup redoes the cheap block-wide rank scan of its sample
 // (T is ~1-2k ids) and then gathers `tok_per_block` token rows; chunk 0 writes status.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void splice_embed_kernel(const long* __restrict__ ids,
-                                                           const h16_t* __restrict__ embed,
-                                                           const h16_t* __restrict__ img,
-                                                           const h16_t* __restrict__ spi,
-                                                           const int* __restrict__ spi_offset,
-                                                           h16_t* __restrict__ out, int* __restrict__ status,
-                                                           int T, int C, int n_patch, long patch_id,
-                                                           long bbox_id, long im_start_id, long im_end_id,
-                                                           int vocab, int tok_per_block) {
-  extern __shared__ int sh[];  // [T] patch rank, [T] bbox rank, [8] scratch
-  int* prank = sh;
-  int* brank = sh + T;
+// The part both splice kernels share: block-wide rank scan of one sample's ids (prank[t] / brank[t] = rank of the
+// <im_patch> / <bbox> token at t among its kind, -1 elsewhere), then the structural checks that need no region count.
+// -> status bits 1, 4, 8, 16 (the same value in every thread); *nb_out = the number of <bbox> tokens of the row.
+__device__ __forceinline__ int splice_scan_row(const long* __restrict__ row, int* prank, int* brank, int T, int n_patch,
+                                               long patch_id, long bbox_id, long im_start_id, long im_end_id,
+                                               int* nb_out) {
   __shared__ int carry[2];
   __shared__ int wsum[2][4];
-  const int b = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long* row = ids + (size_t)b * T;
   if (tid == 0) carry[0] = carry[1] = 0;
   __syncthreads();
   for (int base = 0; base < T; base += 256) {
@@ -444,17 +436,38 @@ __global__ __launch_bounds__(256) void splice_embed_kernel(const long* __restric
   for (int t = tid; t < T; t += 256)
     if (prank[t] >= 0 && t - prank[t] != first) atomicOr(&flags_sh, 16);  // patch run not contiguous
   __syncthreads();
+  int st = flags_sh;
+  const int np = carry[0];
+  *nb_out = carry[1];
+  if (np != 0 && np != n_patch) st |= 1;                       // wrong number of patch tokens
+  if (np > 0) {
+    // ids < 0: a checkpoint without mm_use_im_start_end -- the patch run stands alone (spi_llava.py:158-196)
+    if (im_start_id >= 0 && (first < 1 || row[first - 1] != im_start_id)) st |= 4;    // <im_start> must precede
+    if (im_end_id >= 0 && (first + n_patch >= T || row[first + n_patch] != im_end_id)) st |= 8;  // <im_end> must follow
+  }
+  return st;
+}
+
+__global__ __launch_bounds__(256) void splice_embed_kernel(const long* __restrict__ ids,
+                                                           const h16_t* __restrict__ embed,
+                                                           const h16_t* __restrict__ img,
+                                                           const h16_t* __restrict__ spi,
+                                                           const int* __restrict__ spi_offset,
+                                                           h16_t* __restrict__ out, int* __restrict__ status,
+                                                           int T, int C, int n_patch, long patch_id,
+                                                           long bbox_id, long im_start_id, long im_end_id,
+                                                           int vocab, int tok_per_block) {
+  extern __shared__ int sh[];  // [T] patch rank, [T] bbox rank
+  int* prank = sh;
+  int* brank = sh + T;
+  const int b = blockIdx.y;
+  const int tid = threadIdx.x;
+  const long* row = ids + (size_t)b * T;
+  int nb;
+  int st = splice_scan_row(row, prank, brank, T, n_patch, patch_id, bbox_id, im_start_id, im_end_id, &nb);
   if (tid == 0 && blockIdx.x == 0) {
-    int st = flags_sh;
-    const int np = carry[0], nb = carry[1];
-    if (np != 0 && np != n_patch) st |= 1;                       // wrong number of patch tokens
     const int want = spi_offset ? spi_offset[b + 1] - spi_offset[b] : 0;
     if (nb != want) st |= 2;                                       // #<bbox> != #regions
-    if (np > 0) {
-      // ids < 0: a checkpoint without mm_use_im_start_end -- the patch run stands alone (spi_llava.py:158-196)
-      if (im_start_id >= 0 && (first < 1 || row[first - 1] != im_start_id)) st |= 4;    // <im_start> must precede
-      if (im_end_id >= 0 && (first + n_patch >= T || row[first + n_patch] != im_end_id)) st |= 8;  // <im_end> must follow
-    }
     status[b] = st;
   }
   const int nvec = C >> 3;
@@ -480,6 +493,73 @@ __global__ __launch_bounds__(256) void splice_embed_kernel(const long* __restric
     }
     *reinterpret_cast<uint4v*>(out + ((size_t)b * T + t) * C + v * 8) =
         *reinterpret_cast<const uint4v*>(src + v * 8);
+  }
+}
+
+// The windowed sibling: sample b writes only its positions [lo_b, hi_b) into the compact out[b, 0 .. W) (slot j = position
+// lo_b + j, slots behind the window zero), takes its patch rows from img[img_of_row[b]] ([U, n_patch, C]: rows that show
+// one image share one copy) and owns regions only for the <bbox> tokens of rank >= spi_skip[b] (the earlier ones lie
+// before the window; whoever computed those positions had their features).  The scan and the status cover the WHOLE row.
+// Status bit 2: #<bbox> != spi_skip + #regions; bit 32: a <bbox> inside the window whose rank is below spi_skip.
+// grid = (ceil(W / tok_per_block), samples).  lo / hi / img_of_row are clamped here, so a bad table cannot leave `out`,
+// `img` or the row; the wrapper checks them where their values are known.
+__global__ __launch_bounds__(256) void splice_embed_window_kernel(
+    const long* __restrict__ ids, const h16_t* __restrict__ embed, const h16_t* __restrict__ img,
+    const int* __restrict__ img_of_row, const h16_t* __restrict__ spi, const int* __restrict__ spi_offset,
+    const int* __restrict__ spi_skip, const int* __restrict__ lo_of, const int* __restrict__ hi_of,
+    h16_t* __restrict__ out, int* __restrict__ status, int T, int W, int C, int n_patch, int n_img, long patch_id,
+    long bbox_id, long im_start_id, long im_end_id, int vocab, int tok_per_block) {
+  extern __shared__ int sh[];  // [T] patch rank, [T] bbox rank
+  int* prank = sh;
+  int* brank = sh + T;
+  __shared__ int early_sh;
+  const int b = blockIdx.y;
+  const int tid = threadIdx.x;
+  const long* row = ids + (size_t)b * T;
+  const int lo = min(max(lo_of[b], 0), T);
+  const int n_win = min(min(max(hi_of[b], lo), T) - lo, W);
+  const int skip = max(spi_skip[b], 0);
+  if (tid == 0) early_sh = 0;
+  int nb;
+  int st = splice_scan_row(row, prank, brank, T, n_patch, patch_id, bbox_id, im_start_id, im_end_id, &nb);
+  if (blockIdx.x == 0) {
+    for (int t = lo + tid; t < lo + n_win; t += 256)
+      if (brank[t] >= 0 && brank[t] < skip) early_sh = 1;         // a <bbox> of the window nobody has features for
+    __syncthreads();
+    if (tid == 0) {
+      const int want = skip + (spi_offset ? spi_offset[b + 1] - spi_offset[b] : 0);
+      if (nb != want) st |= 2;                                     // #<bbox> != skipped + #regions
+      if (early_sh) st |= 32;
+      status[b] = st;
+    }
+  }
+  const int nvec = C >> 3;
+  const int so = spi_offset ? spi_offset[b] : 0;
+  const int n_region = spi_offset ? spi_offset[b + 1] - so : 0;
+  const int im = n_img > 0 ? min(max(img_of_row[b], 0), n_img - 1) : 0;
+  const int j0 = blockIdx.x * tok_per_block;
+  const int j1 = min(W, j0 + tok_per_block);
+  const uint4v zero = {0u, 0u, 0u, 0u};
+  for (int i = j0 * nvec + tid; i < j1 * nvec; i += 256) {
+    const int j = i / nvec, v = i % nvec;
+    uint4v piece = zero;
+    if (j < n_win) {
+      const int t = lo + j;
+      const int r = brank[t] - skip;
+      const h16_t* src;
+      if (prank[t] >= 0 && prank[t] < n_patch)
+        src = img + ((size_t)im * n_patch + prank[t]) * C;
+      else if (brank[t] >= 0 && r >= 0 && r < n_region && spi)
+        src = spi + ((size_t)so + r) * C;
+      else {
+        long id = row[t];
+        if (id < 0) id = 0;
+        if (id >= vocab) id = vocab - 1;
+        src = embed + (size_t)id * C;
+      }
+      piece = *reinterpret_cast<const uint4v*>(src + v * 8);
+    }
+    *reinterpret_cast<uint4v*>(out + ((size_t)b * W + j) * C + v * 8) = piece;
   }
 }
 
@@ -809,6 +889,26 @@ int g4r_splice_embed_bf16(const long* ids, const void* embed, const void* img, c
                      spi_offset, (h16_t*)out, status, T, C, n_patch, patch_id, bbox_id, im_start_id, im_end_id,
                      vocab, tpb);
   G4R_CHECK_LAUNCH("splice_embed");
+  return G4R_OK;
+}
+
+int g4r_splice_embed_window_bf16(const long* ids, const void* embed, const void* img, const int* img_of_row,
+                                 const void* spi, const int* spi_offset, const int* spi_skip, const int* lo,
+                                 const int* hi, void* out, int* status, int B, int T, int W, int C, int n_patch,
+                                 int n_img, long patch_id, long bbox_id, long im_start_id, long im_end_id, int vocab,
+                                 void* stream) {
+  G4R_REQUIRE(B > 0 && T > 0 && C % 8 == 0 && vocab > 0 && n_patch >= 0, "splice_embed_window: bad shape");
+  G4R_REQUIRE(T <= 16384, "splice_embed_window: T <= 16384");
+  G4R_REQUIRE(W >= 1, "splice_embed_window: W >= 1");
+  G4R_REQUIRE(ids && embed && out && status, "splice_embed_window: null pointer");
+  G4R_REQUIRE(img_of_row && spi_skip && lo && hi, "splice_embed_window: window tables missing");
+  G4R_REQUIRE(n_patch == 0 || (img && n_img >= 1), "splice_embed_window: image features missing");
+  const int tpb = 4;
+  hipLaunchKernelGGL(splice_embed_window_kernel, dim3(g4r_ceil_div(W, tpb), B), dim3(256), 2 * T * sizeof(int),
+                     (hipStream_t)stream, ids, (const h16_t*)embed, (const h16_t*)img, img_of_row, (const h16_t*)spi,
+                     spi_offset, spi_skip, lo, hi, (h16_t*)out, status, T, W, C, n_patch, n_img, patch_id, bbox_id,
+                     im_start_id, im_end_id, vocab, tpb);
+  G4R_CHECK_LAUNCH("splice_embed_window");
   return G4R_OK;
 }
 

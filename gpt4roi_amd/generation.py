@@ -214,6 +214,136 @@ def plan_shared_prefix(rows_ids, same_image, rows_boxes, bbox_id):
     return P
 
 
+# ---- encoded images: the vision path and the fused pyramid run once per picture, not per row or per turn ---------------
+@dataclass(eq=False)
+class EncodedImage:
+    """What the model computes from ONE image and nothing else (the class lives here, beside the host functions that group
+    and compare images; spi_llava re-exports it): made by SPILlavaLlamaModel.encode_image, read through
+    SPILlavaLlamaModel.features_of (which re-encodes from `pixels` when a stamp no longer matches the model), accepted
+    wherever generate() takes `images`.  Inference only.
+
+    pixels [3, S, S]: a detached copy of the input.  tokens [n_patch, C]: the projected patch tokens the splice reads.
+    maps / affs: the four raw maps of the fused pyramid ([1, H_l, H_l, E], H_l = 8P, 4P, 2P, P) and their deferred
+    GroupNorm + ReLU affines ([1, 2, E] fp32) -- what RoIAlign pools any box from.  P: tokens per side; image_size = 14 P;
+    dtype: the 16-bit storage type.  tower / spi_stamp / proj_stamp: the vision tower object and the parameter stamps
+    (data pointer and version counter of every region-module / projector parameter) the features were computed with.
+    The tower is watched by IDENTITY only (it is frozen and keeps 16-bit copies without version stamps): weights loaded
+    in place into the same ClipVisionTower object leave an encoding stale without any sign -- encode again after that.
+
+    Memory: the maps hold 85 P^2 positions of E 16-bit channels, 85 * P^2 * E * 2 bytes -- 100 MB for a 336^2 image at
+    E = 1024 (P = 24), 25 MB at 224^2 -- plus n_patch * C * 2 bytes of patch tokens (4.7 MB at 336^2, C = 4096) and the
+    fp32 pixels (1.4 MB).  Equality is identity (two encodings of equal pixels are two objects;
+    generation.same_pixels compares the pixels)."""
+    pixels: torch.Tensor
+    tokens: torch.Tensor
+    maps: list
+    affs: list
+    P: int
+    image_size: int
+    dtype: torch.dtype
+    tower: object
+    spi_stamp: tuple
+    proj_stamp: tuple
+    encodes: int = 1                                # how often the features were computed (1 + the re-encodes)
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in [self.pixels, self.tokens] + list(self.maps) + list(self.affs))
+
+
+def is_encoded(image):
+    return isinstance(image, EncodedImage)
+
+
+def _pixels(image):
+    """The [3, S, S] pixel tensor a row shows: the tensor itself, or the copy an EncodedImage keeps."""
+    x = image.pixels if is_encoded(image) else image
+    return x[0] if x.dim() == 4 and x.size(0) == 1 else x
+
+
+def same_pixels(a, b):
+    """Two rows show one image iff they are the same EncodedImage object or their pixel tensors agree in shape, dtype,
+    device and every value (`torch.equal`)."""
+    if a is b:
+        return True
+    x, y = _pixels(a), _pixels(b)
+    return x.shape == y.shape and x.dtype == y.dtype and x.device == y.device and bool(torch.equal(x, y))
+
+
+def group_images(images):
+    """The rows of a batch grouped by the image they show: -> (unique, image_of_row).  images: a [B, 3, S, S] tensor or a
+    sequence of B entries, each a [3, S, S] pixel tensor or an EncodedImage; rows are equal as `same_pixels` says.
+    unique lists one entry per distinct image in order of first appearance -- the EncodedImage of the group when any of its
+    rows brought one (nothing is left to compute for it), else the first row's pixel tensor -- and image_of_row[b] indexes
+    it.  Pure host function (one comparison per row and earlier distinct image)."""
+    rows = [images] if is_encoded(images) else list(images)
+    unique, image_of_row = [], []
+    for r in rows:
+        for u, have in enumerate(unique):
+            if same_pixels(have, r):
+                if is_encoded(r) and not is_encoded(have):
+                    unique[u] = r
+                image_of_row.append(u)
+                break
+        else:
+            unique.append(r)
+            image_of_row.append(len(unique) - 1)
+    return unique, image_of_row
+
+
+@dataclass
+class WindowPlan:
+    """What one windowed splice (SPILlavaLlamaModel.embed_window) is told, per row: positions [lo, hi) are written;
+    region_from = the ordinal of the first box that goes through the region head = spi_skip, the number of leading `<bbox>`
+    tokens the splice kernel finds no feature row for (both are the number of `<bbox>` tokens before lo).  W = the widest
+    window (at least 1): the stride of the compact output."""
+    lo: list
+    hi: list
+    region_from: list
+    spi_skip: list
+    W: int
+
+
+def plan_windows(rows_ids, lo, hi, bbox_id):
+    """rows_ids: the real (unpadded) ids of every row; lo / hi: one int for all rows or one per row, hi None = each row's
+    length.  ValueError unless 0 <= lo <= hi <= len(row).  Pure host function."""
+    rows_ids = [list(r) for r in rows_ids]
+    B = len(rows_ids)
+    lo = [int(x) for x in lo] if isinstance(lo, (list, tuple)) else [int(lo)] * B
+    hi = [len(r) for r in rows_ids] if hi is None else \
+        ([int(x) for x in hi] if isinstance(hi, (list, tuple)) else [int(hi)] * B)
+    if len(lo) != B or len(hi) != B:
+        raise ValueError(f"{len(lo)} / {len(hi)} window bounds for {B} rows")
+    for r, a, z in zip(rows_ids, lo, hi):
+        if not 0 <= a <= z <= len(r):
+            raise ValueError(f"window [{a}, {z}) of a row of {len(r)} tokens")
+    before = [sum(1 for t in r[:a] if t == bbox_id) for r, a in zip(rows_ids, lo)]
+    return WindowPlan(lo, hi, before, list(before), max([1] + [z - a for a, z in zip(lo, hi)]))
+
+
+def plan_shared_windows(rows_ids, P, bbox_id):
+    """The two splices of a shared-prefix batch whose images are encoded once: -> (prefix, suffix).  prefix: ONE row, row 0,
+    over [0, P); its region_from is 0 when a `<bbox>` lies before P (row 0's boxes then go through the region head, once for
+    the whole batch) and the row's `<bbox>` count otherwise (no box is needed: the region head does not run).  suffix: every
+    row over [P, n_b), region_from = the number of `<bbox>` tokens before P.
+    Known redundancy: a window skips LEADING boxes only (the splice's count check is #<bbox> == spi_skip + #regions), so
+    when a `<bbox>` lies before P the prefix call sends ALL of row 0's boxes through the region head, and those of them
+    that sit at or behind P go through it a second time with the suffixes.  Correct, and one row's trailing boxes at
+    most; the boxes before P still run once instead of B times."""
+    rows_ids = [list(r) for r in rows_ids]
+    suffix = plan_windows(rows_ids, P, None, bbox_id)
+    prefix = plan_windows(rows_ids[:1], 0, P, bbox_id)
+    if suffix.region_from[0] == 0:
+        n0 = sum(1 for t in rows_ids[0] if t == bbox_id)
+        prefix.region_from, prefix.spi_skip = [n0], [n0]
+    return prefix, suffix
+
+
+def plan_session_window(new_ids, L, bbox_id):
+    """A session turn that keeps L cache rows splices only [L, T): the boxes whose `<bbox>` sits at or behind L go through
+    the region head (none: it does not run)."""
+    return plan_windows([list(new_ids)], L, None, bbox_id)
+
+
 def right_padded_lengths(attention_mask, B, T):
     """The rows' real lengths of a RIGHT-padded [B, T] mask (None: all T) as a list of ints; ValueError for any other mask
     (left padding, holes, an empty row).  One small device->host read."""
@@ -256,11 +386,17 @@ class GenerationSession:
     next to the reference's `history_cache` (app.py), and hands it to every turn.
 
     ids / image / boxes: the token ids whose K/V the cache holds (truncated to the decoder's row count), the image tensor
-    and the per-`<bbox>` boxes they were computed with.  decoder / stamp: the decoder they live in and its `cache_version`
+    (with cache_image=True: its EncodedImage) and the per-`<bbox>` boxes they were computed with.  decoder / stamp: the decoder they live in and its `cache_version`
     when the session last wrote it -- a session that meets another decoder, or a cache somebody else has reset or written
     since, is treated as empty.  reused / prefilled: cache rows kept / prompt positions prefilled by the last call."""
 
-    def __init__(self):
+    def __init__(self, cache_image=False):
+        """cache_image: keep the conversation's picture as an EncodedImage (what generate() computed from it: projected
+        patch tokens and the fused pyramid, about 105 MB at 336^2, see SPILlavaLlamaModel.encode_image) in place of the
+        pixel copy.  A turn on the same image then runs no ViT and no fuse round, splices only the positions it prefills
+        and runs the region head only for boxes whose `<bbox>` lies there.  One image per session: another image
+        replaces the entry.  Default False: the session holds and does what it did before."""
+        self.cache_image = bool(cache_image)
         self.clear()
         self.reused = 0
         self.prefilled = 0
@@ -277,6 +413,8 @@ class GenerationSession:
         image trusts nothing: a text-only conversation runs as without a session."""
         if self.image is None or image is None:
             return False
+        if is_encoded(self.image) or is_encoded(image):
+            return same_pixels(self.image, image)
         return self.image.shape == image.shape and self.image.dtype == image.dtype and \
             self.image.device == image.device and bool(torch.equal(self.image, image))
 
@@ -291,7 +429,9 @@ class GenerationSession:
         """After a decode: the cache holds the prompt and the generated tokens that were fed back (`decoder.rows_held`)."""
         prompt_ids = list(prompt_ids)
         self.ids = (prompt_ids + list(new_ids))[:int(decoder.rows_held)]
-        if image is None or not self.same_image(image):
+        if is_encoded(image):                                    # cache_image: the encoding (it owns a copy of the pixels)
+            self.image = image
+        elif image is None or not self.same_image(image):
             self.image = None if image is None else image.detach().clone()
         self.boxes = [list(b) for b in boxes]
         self.decoder, self.stamp = decoder, decoder.cache_version

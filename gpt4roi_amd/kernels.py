@@ -82,6 +82,8 @@ _SIGS = {
     "g4r_swiglu_bf16": [P, P, c_int, c_int, P],
     "g4r_splice_embed_bf16": [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_long, c_long, c_long,
                               c_long, c_int, P],
+    "g4r_splice_embed_window_bf16": [P, P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_long,
+                                     c_long, c_long, c_long, c_int, P],
     "g4r_argmax_rows_f32": [P, c_long, c_int, c_int, P, P],
     "g4r_add_rows_bf16": [P, P, P, c_long, c_int, c_long, P],
     "g4r_cast_f32_to_bf16": [P, P, c_long, P],
@@ -1081,6 +1083,46 @@ def splice_embed(ids, embed, img, spi, spi_offset, n_patch, patch_id, bbox_id, i
         _p(ids), _p(embed), _p(img), _p(spi), _p(spi_offset), _p(out), _p(status),
                                       B, T, C, n_patch if img is not None else 0, patch_id, bbox_id,
                                       im_start_id, im_end_id, embed.size(0), _stream(ids),), dt=dt)
+    return out, status
+
+
+def splice_embed_window(ids, embed, img, img_of_row, spi, spi_offset, spi_skip, lo, hi, W, n_patch, patch_id, bbox_id,
+                        im_start_id, im_end_id, out=None):
+    """The windowed splice: row b's positions [lo[b], hi[b]) -> out[b, :hi[b] - lo[b]] of the compact (out [B,W,C], status
+    int32 [B]); the slots behind a row's window are zeros.  ids [B,T] int64; embed [V,C]; img [U,n_patch,C] or None, row b
+    reads img[img_of_row[b]]; spi [N,C] or None with spi_offset int32 [B+1] (device) or None; spi_skip[b] = how many leading
+    <bbox> tokens of row b have no row in spi (their positions lie before the window).  img_of_row / spi_skip / lo / hi:
+    sequences of B ints, checked here (0 <= lo <= hi <= T, hi - lo <= W, 0 <= img_of_row < U, spi_skip >= 0; ValueError)
+    and sent to the device in one copy."""
+    dt = _h16(embed, img, spi)
+    _lib.require_gpu(ids)
+    assert ids.dtype == torch.int64 and ids.is_contiguous()
+    B, T = ids.shape
+    C = embed.size(1)
+    W = int(W)
+    if W < 1:
+        raise ValueError(f"splice_embed_window: W = {W}, has to be >= 1")
+    U = 0 if img is None else int(img.size(0))
+    if img is not None:
+        assert img.dim() == 3 and img.is_contiguous() and img.size(1) == n_patch and img.size(2) == C
+    rows = [[int(x) for x in r] for r in (img_of_row, spi_skip, lo, hi)]
+    if any(len(r) != B for r in rows):
+        raise ValueError(f"splice_embed_window: img_of_row / spi_skip / lo / hi need {B} entries each")
+    for b, (u, k, a, z) in enumerate(zip(*rows)):
+        if not 0 <= a <= z <= T or z - a > W:
+            raise ValueError(f"splice_embed_window: row {b}: window [{a}, {z}) outside 0 <= lo <= hi <= {T} or wider than W = {W}")
+        if k < 0 or (U > 0 and not 0 <= u < U):
+            raise ValueError(f"splice_embed_window: row {b}: img_of_row = {u} (of {U} images), spi_skip = {k}")
+    tab = torch.tensor(rows, dtype=torch.int32).to(ids.device)
+    if out is None:
+        out = torch.empty((B, W, C), dtype=dt, device=ids.device)
+    else:
+        assert out.dtype == dt and tuple(out.shape) == (B, W, C) and out.is_contiguous()
+    status = torch.empty((B,), dtype=torch.int32, device=ids.device)
+    _launch("g4r_splice_embed_window_bf16", (
+        _p(ids), _p(embed), _p(img), _p(tab[0]), _p(spi), _p(spi_offset), _p(tab[1]), _p(tab[2]), _p(tab[3]), _p(out),
+        _p(status), B, T, W, C, n_patch if img is not None else 0, U, patch_id, bbox_id, im_start_id, im_end_id,
+        embed.size(0), _stream(ids),), dt=dt)
     return out, status
 
 

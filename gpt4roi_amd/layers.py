@@ -220,8 +220,11 @@ class PreparedBoxes:
     the [img_id, box * image_size] RoI table of layers.py:295-302, the raw normalised boxes for
     pos_embedd (layers.py:284-285), the per-image counts and their prefix sums (for the splice)."""
 
-    def __init__(self, bboxes, image_size, device, dtype=torch.bfloat16):
-        """dtype: the 16-bit storage type of the request.  torch.float16 reproduces the serving path of the reference, where
+    def __init__(self, bboxes, image_size, device, dtype=torch.bfloat16, image_of_row=None):
+        """image_of_row: None, or a list of len(bboxes) ints -- `rois5[:, 0]` of row b's boxes is then image_of_row[b]
+        instead of b, so the boxes of B rows can pool from U < B pyramids (rows that show one image share its maps);
+        `counts` / `offsets` stay per row.
+        dtype: the 16-bit storage type of the request.  torch.float16 reproduces the serving path of the reference, where
         the boxes arrive as `.half()` (app.py:271): `single_img_roi * 224` (layers.py:297) is then a HALF product, rounded
         to fp16 before RoIAlign's `.to(float32)` (layers.py:311).  With bf16 (the training dtype, where the dataset hands
         fp32 boxes) the product stays fp32."""
@@ -231,7 +234,13 @@ class PreparedBoxes:
         n = sum(self.counts)
         src = bboxes[0].device if self.num_imgs else torch.device("cpu")
         boxes = torch.cat([b.detach().float() for b in bboxes], 0) if n else torch.zeros(0, 4, device=src)
-        img_id = torch.cat([torch.full((c,), float(i), device=src) for i, c in enumerate(self.counts)]) \
+        if image_of_row is None:
+            image_of_row = range(self.num_imgs)
+        else:
+            image_of_row = [int(i) for i in image_of_row]
+            if len(image_of_row) != self.num_imgs or any(i < 0 for i in image_of_row):
+                raise ValueError(f"image_of_row: {self.num_imgs} non-negative image indices wanted, got {image_of_row}")
+        img_id = torch.cat([torch.full((c,), float(i), device=src) for i, c in zip(image_of_row, self.counts)]) \
             if self.num_imgs else torch.zeros(0, device=src)
         scaled = (boxes.to(torch.float16) * float(image_size)).float() if dtype is torch.float16 else boxes * float(image_size)
         self.rois5 = torch.cat([img_id[:, None], scaled], 1).contiguous().to(device)
@@ -510,12 +519,35 @@ class MLVLROIQueryModule(nn.Module):
                 out = _RegionModuleFn.apply(self, mlvl_feats, bboxes, tuple(k for k, _ in named), *[p for _, p in named])
                 counts = bboxes.counts if isinstance(bboxes, PreparedBoxes) else [int(b.size(0)) for b in bboxes]
                 return list(torch.split(out, counts, 0))
-        with torch.no_grad():
-            toks, P, sizes = self._tokens(mlvl_feats)
-            maps, affs = self.mlvl_fuse(toks, P, sizes)
-            if isinstance(bboxes, PreparedBoxes):
-                assert bboxes.image_size == 14 * P, "PreparedBoxes built for another image size"
-            return self.roi_align(maps, bboxes, affines=affs, image_size=14 * P)
+        return self._extract(*self._fuse(mlvl_feats), bboxes)
+
+    @torch.no_grad()
+    def fuse(self, mlvl_feats):
+        """The half of the inference forward that depends on the image alone: the four input convs and the five fuse
+        rounds.  -> (maps: list[4] of raw conv maps [B, H_l, H_l, C], affs: their deferred GroupNorm + ReLU affines
+        [B, 2, C] fp32) -- what `extract` pools from, for any boxes, as often as wanted."""
+        self._maybe_prepare()
+        return self._fuse(mlvl_feats)
+
+    @torch.no_grad()
+    def _fuse(self, mlvl_feats):
+        toks, P, sizes = self._tokens(mlvl_feats)
+        return self.mlvl_fuse(toks, P, sizes)
+
+    @torch.no_grad()
+    def extract(self, maps, affs, bboxes):
+        """The half that depends on the boxes: RoIAlign over `fuse`'s maps and the region head.  bboxes: list of [n_i, 4]
+        normalised xyxy or a PreparedBoxes (whose image_of_row may point several rows at one of the maps' images).
+        -> list of [n_i, out_dims]."""
+        self._maybe_prepare()
+        return self._extract(maps, affs, bboxes)
+
+    @torch.no_grad()
+    def _extract(self, maps, affs, bboxes):
+        image_size = 14 * maps[-1].size(1)                     # the coarsest level is the P x P token grid
+        if isinstance(bboxes, PreparedBoxes):
+            assert bboxes.image_size == image_size, "PreparedBoxes built for another image size"
+        return self.roi_align(maps, bboxes, affines=affs, image_size=image_size)
 
 
 class _RegionModuleFn(torch.autograd.Function):

@@ -539,7 +539,7 @@ class LlamaDecoder:
                                                     splits=K.shared_attn_splits(self.heads, batch), batch=batch)
         return pool[batch]
 
-    def _prefill_shared(self, inputs_embeds, key_padding_mask, P, max_new_tokens):
+    def _prefill_shared(self, inputs_embeds, key_padding_mask, P, max_new_tokens, prefix_embeds=None):
         """Prefill of decode_graph_batch(shared_prefix=P): -> (step-0 logits [B, V], the rows' lengths n_b).  Existing
         kernels only: the prefix once at batch 1 into slot 0, its K/V rows copied to the other slots (so the per-row ragged
         kernel stays usable on the same cache), then the B right-padded suffix blocks through the dense forward at position
@@ -548,6 +548,11 @@ class LlamaDecoder:
             raise ValueError("shared_prefix: inputs_embeds must be [B, T, C]")
         B, T, C = inputs_embeds.shape
         P = int(P)
+        if prefix_embeds is not None:
+            # the two blocks arrive apart: prefix_embeds [1, P, C] and inputs_embeds = the suffixes [B, T - P, C]
+            if tuple(prefix_embeds.shape) != (1, P, C) or P < 1:
+                raise ValueError(f"shared_prefix = {P}: prefix_embeds must be [1, {P}, {C}], got {tuple(prefix_embeds.shape)}")
+            T += P
         if key_padding_mask is None:
             lens = [T] * B
         else:
@@ -565,10 +570,11 @@ class LlamaDecoder:
                              f"{self.max_positions} cache rows")
         self.reset(B)
         if P > 0:
-            self.forward(inputs_embeds[:1, :P], return_hidden=True)          # slot 0, positions [0, P)
+            self.forward(inputs_embeds[:1, :P] if prefix_embeds is None else prefix_embeds, return_hidden=True)   # slot 0, [0, P)
             self.kc[:, 1:B, :P].copy_(self.kc[:, :1, :P].expand(-1, B - 1, -1, -1))
             self.vc[:, 1:B, :P].copy_(self.vc[:, :1, :P].expand(-1, B - 1, -1, -1))
-        xn = self.forward(inputs_embeds[:, P:], return_hidden=True)          # [B, T - P, C] at positions P ..
+        # [B, T - P, C] at positions P ..
+        xn = self.forward(inputs_embeds[:, P:] if prefix_embeds is None else inputs_embeds, return_hidden=True)
         last = torch.tensor([b * (T - P) + n - 1 - P for b, n in enumerate(lens)], dtype=torch.int32, device=xn.device)
         rows = K.gather_rows(xn.reshape(B * (T - P), C), last)
         logits = K.gemm(rows, self.lm_head, out_dtype=torch.float32)
@@ -608,7 +614,7 @@ class LlamaDecoder:
 
     @torch.no_grad()
     def decode_graph(self, inputs_embeds, max_new_tokens, stop_ids=(), check_every=32, use_graph=True, sampler=None,
-                     seed=0, on_tokens=None, past_len=0):
+                     seed=0, on_tokens=None, past_len=0, embeds_from=0):
         """generate() for batch 1 with the per-token loop on the device: prefill eagerly, then replay one captured
         hipGraph per token (token id, position, output slot, sampling seed and step live in device memory).
         sampler = None (greedy) or (temperature, top_k, top_p); the uniform of step s is Philox(seed, s).
@@ -616,14 +622,19 @@ class LlamaDecoder:
         (inclusive); `on_tokens(list of new ids) -> bool` is the hook for HF-style stopping criteria.
         past_len = L > 0: the first L cache rows already hold the K/V of inputs_embeds[:, :L] (see `rewind`): no reset, only
         inputs_embeds[:, L:] is prefilled, at position L; everything after the prefill is the same.  Afterwards `rows_held`
-        says how many cache rows hold known tokens: the prompt and every generated token but the last (never fed back)."""
+        says how many cache rows hold known tokens: the prompt and every generated token but the last (never fed back).
+        embeds_from = F <= L (default 0): inputs_embeds holds only the positions [F, T) of the prompt -- a caller that knows L
+        need not splice what the cache already holds (SPILlavaLlamaModel.embed_window)."""
         assert inputs_embeds.size(0) == 1
-        past_len = int(past_len)
+        past_len, embeds_from = int(past_len), int(embeds_from)
+        if not 0 <= embeds_from <= past_len:
+            raise ValueError(f"embeds_from = {embeds_from}: has to lie in [0, past_len = {past_len}]")
         if past_len > 0:
-            if not past_len < inputs_embeds.size(1):
-                raise ValueError(f"past_len = {past_len} leaves nothing of the {inputs_embeds.size(1)} positions to prefill")
+            if not past_len < embeds_from + inputs_embeds.size(1):
+                raise ValueError(f"past_len = {past_len} leaves nothing of the {embeds_from + inputs_embeds.size(1)} positions "
+                                 "to prefill")
             self.rewind(past_len)
-            logits = self.forward(inputs_embeds[:, past_len:], all_logits=False)
+            logits = self.forward(inputs_embeds[:, past_len - embeds_from:], all_logits=False)
         else:
             self.reset(1)
             logits = self.forward(inputs_embeds, all_logits=False)
@@ -744,7 +755,7 @@ class LlamaDecoder:
     @torch.no_grad()
     def decode_graph_batch(self, inputs_embeds, max_new_tokens, stop_ids=(), use_graph=True, key_padding_mask=None,
                            sampler=None, seeds=None, on_tokens=None, check_every=None, shared_prefix=None,
-                           own_positions=None):
+                           own_positions=None, prefix_embeds=None):
         """generate() for B sequences, per-token loop on the device.  Prompts of equal length, or -- with
         key_padding_mask (bool [B, T]) -- prompts padded to a common T on either side (HF batch generation pads on the
         left; merged serving requests of different lengths pad on the right): see `forward`.  Prefill
@@ -775,7 +786,9 @@ class LlamaDecoder:
         unless all rows have one length.  Each decode step attends with kernels.attn_decode_shared (prefix K/V read once
         per group of 16 rows) where kernels.shared_attn_wins(B, P, heads, head_dim) says so, else with the ragged
         attn_decode at rope_pos_dev=None; the captured graph is kept per (B, route) and serves any P (P lives in device
-        memory).  own_positions=True takes this path with P = 0 (an empty prefix).  Sampling, seeds, on_tokens, stopping
+        memory).  prefix_embeds [1, P, C] (with shared_prefix = P >= 1): the prefix block on its own; inputs_embeds is then
+        the suffix block [B, T - P, C] (row b's positions [P, n_b), then padding) while key_padding_mask keeps its [B, T]
+        layout -- for a caller that never built the B copies of the prefix.  own_positions=True takes this path with P = 0 (an empty prefix).  Sampling, seeds, on_tokens, stopping
         and the pos / rows_held = 0 / cache_version contracts are those of the masked batch."""
         from .generation import expand_seeds, row_samplers
         B = inputs_embeds.size(0)
@@ -783,13 +796,15 @@ class LlamaDecoder:
         shared = bool(own_positions) if own_positions is not None else P >= 1
         if P >= 1 and not shared:
             raise ValueError("shared_prefix >= 1 runs at the rows' own positions: own_positions=False contradicts it")
+        if prefix_embeds is not None and P < 1:
+            raise ValueError("prefix_embeds= comes with shared_prefix = P >= 1")
         rows = row_samplers(sampler, B)
         sampled = any(r is not None for r in rows)
         early = sampled or on_tokens is not None
         every = max(1, int(check_every)) if check_every is not None else 32
         lens = route = None
         if shared:
-            logits, lens = self._prefill_shared(inputs_embeds, key_padding_mask, P, max_new_tokens)
+            logits, lens = self._prefill_shared(inputs_embeds, key_padding_mask, P, max_new_tokens, prefix_embeds)
             self.shared_step0_logits = logits                           # [B, V] fp32, for tools and tests
             T = max(lens)
             route = bool(K.shared_attn_wins(B, P, self.heads, self.head_dim))

@@ -142,7 +142,9 @@ class ConversationBot:
             session=None):
         """One question -> (answer text or None, error message or None, history_cache)   (app.py:243-328, no UI state).
         session: a generation.GenerationSession the caller keeps next to `history_cache`, one per conversation; with it a
-        follow-up turn prefills only the tokens the KV cache does not hold yet (same answers, see generate)."""
+        follow-up turn prefills only the tokens the KV cache does not hold yet (same answers, see generate); a
+        GenerationSession(cache_image=True) also keeps the picture's encoding, so a follow-up on the same picture runs no
+        vision tower and no fuse round."""
         error, text = self.check_input(text, image, history_cache)
         if error is not None:
             return None, error, history_cache
@@ -215,7 +217,7 @@ class ConversationBot:
         return results, rows, batch
 
     def run_batch(self, texts, images, history_caches, do_sample=True, temperature=0.2, max_new_tokens=1024, seeds=None,
-                  share_prefix=False):
+                  share_prefix=False, share_images=False):
         """Several conversations, one question each, answered by ONE batched generate(): -> list of
         (answer or None, error or None, history_cache), one per conversation.  Each conversation is checked and assembled
         as `run` does it; those that fail the check return their error and stay out of the batch.  The prompts are
@@ -227,7 +229,11 @@ class ConversationBot:
         share_prefix: the batch is built RIGHT-padded and generated with shared_prefix=True -- several questions about one
         image share the system header and the image tokens, which are then prefilled once and read once per decode step
         for the whole batch; every conversation is computed at its own positions, as `run` computes it.  Conversations
-        about different images share nothing (P = 0) and still decode together.  Answers and histories as above."""
+        about different images share nothing (P = 0) and still decode together.  Answers and histories as above.
+        share_images (with share_prefix): generate(share_images=True) -- every distinct picture of the batch goes through the
+        vision tower and the fuse rounds once, at batch 1, whatever the number of conversations about it."""
+        if share_images and not share_prefix:
+            raise ValueError("share_images=True goes with share_prefix=True")
         results, rows, batch = self.batch_inputs(texts, images, history_caches, pad_side="right" if share_prefix else "left")
         if not rows:
             return results
@@ -248,7 +254,9 @@ class ConversationBot:
                 new = model.generate(input_ids, images=batch['images'], attention_mask=batch['attention_mask'],
                                      do_sample=do_sample, temperature=temperature, max_new_tokens=max_new_tokens,
                                      stopping_criteria=[criteria], seed=seeds, pad_token_id=self.tokenizer.pad_token_id,
-                                     return_new_tokens=True, **(dict(shared_prefix=True) if share_prefix and len(rows) > 1 else {}))
+                                     return_new_tokens=True,
+                                     **(dict(shared_prefix=True, **(dict(share_images=True) if share_images else {}))
+                                        if share_prefix and len(rows) > 1 else {}))
             finally:
                 model.forward = model.orig_forward
         if len(rows) == 1:

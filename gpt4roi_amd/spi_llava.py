@@ -38,9 +38,10 @@ import torch
 import torch.nn as nn
 
 from . import kernels as K
-from .generation import (GenerationSession, KeywordsStoppingCriteria, SamplingConfig,  # noqa: F401 (re-exported)
-                         StoppingCriteria, _batch_box_rows, _box_rows, dense_or_mask, expand_seeds, plan_shared_prefix,
-                         prepare_inputs_for_generation, right_padded_lengths)
+from .generation import (EncodedImage, GenerationSession, KeywordsStoppingCriteria, SamplingConfig,  # noqa: F401 (re-exported)
+                         StoppingCriteria, _batch_box_rows, _box_rows, dense_or_mask, expand_seeds, group_images, is_encoded,
+                         plan_session_window, plan_shared_prefix, plan_shared_windows, plan_windows,
+                         prepare_inputs_for_generation, right_padded_lengths, same_pixels)
 from .layers import MLVLROIQueryModule, PreparedBoxes
 from .llama import LlamaDecoder
 from .vit import ClipVisionTower
@@ -277,6 +278,12 @@ class SPILlavaLlamaModel(nn.Module):
         run_vision = images is not None and T != 1
         img_tok, spi, off = None, None, None
         n_patch = 0
+        if run_vision and (is_encoded(images) or (isinstance(images, (list, tuple)) and any(is_encoded(i) for i in images))):
+            # images that arrive encoded: no ViT, no fuse round; the whole prompt is the window
+            uniq, image_of_row = group_images(images)
+            if len(image_of_row) != B:
+                raise ValueError(f"{len(image_of_row)} images for a batch of {B} sequences")
+            return self.embed_window(input_ids, [self.encode_image(u) for u in uniq], image_of_row, bboxes)
         if run_vision:
             tower = self.vision_tower[0]
             if isinstance(images, (list, tuple)):
@@ -298,6 +305,135 @@ class SPILlavaLlamaModel(nn.Module):
                                         cfg.im_patch_token, cfg.bbox_token, cfg.im_start_token, cfg.im_end_token)
         self.last_status = status
         return embeds
+
+    # ---- an image encoded once: ViT, projector and the fused pyramid kept for any number of rows and turns ----------
+    def _proj_stamp(self):
+        return tuple((p.data_ptr(), p._version) for p in self.mm_projector.parameters())
+
+    def _refuse_under_grad(self):
+        if torch.is_grad_enabled() and self.trainable_named():
+            raise ValueError("an EncodedImage is for inference: its features are constants, so the trainable parameters "
+                             "behind them would get no gradient (call under torch.no_grad(), or pass the pixels)")
+
+    def _encode(self, pixels):
+        """-> (tokens [n_patch, C], maps, affs, P) of one image [1, 3, S, S]: the launches of embed_inputs at batch 1"""
+        tower = self.vision_tower[0]
+        keep = tower.forward(pixels)
+        image_features, mlvl = tower.select(keep)
+        maps, affs = self.spi_module.fuse(mlvl)
+        tokens = torch.empty((image_features.size(1), self.llama.hidden), dtype=self.dtype, device=pixels.device)
+        K.gemm(image_features[0], self._proj[0], bias=self._proj[1], out=tokens)
+        return tokens, list(maps), list(affs), int(maps[-1].size(1))
+
+    @torch.no_grad()
+    def encode_image(self, image):
+        """image [3, S, S] or [1, 3, S, S] -> EncodedImage (an EncodedImage is returned as it is).  Always batch 1: vision
+        tower, `select`, `mm_projector`, `spi_module.fuse` -- everything of the vision path that depends on the image
+        alone, so that B rows or any number of turns on one picture pay for it once.  Keeps about 105 MB per 336^2 image
+        (see EncodedImage); the caller decides how many to hold."""
+        if is_encoded(image):
+            return image
+        if image.dim() == 3:
+            image = image[None]
+        if image.dim() != 4 or image.size(0) != 1 or image.size(1) != 3 or image.size(2) != image.size(3):
+            raise ValueError(f"encode_image takes ONE image [3, S, S] or [1, 3, S, S], got {tuple(image.shape)}")
+        self._maybe_prepare()
+        tokens, maps, affs, P = self._encode(image)
+        return EncodedImage(pixels=image[0].detach().clone(), tokens=tokens, maps=maps, affs=affs, P=P, image_size=14 * P,
+                            dtype=self.dtype, tower=self.vision_tower[0], spi_stamp=self.spi_module._param_stamp(),
+                            proj_stamp=self._proj_stamp())
+
+    def features_of(self, enc):
+        """-> (tokens, maps, affs) of an EncodedImage, valid for the model as it is NOW: when the vision tower is another
+        object, a region-module or projector parameter was written since (an optimizer step, load_state_dict, an in-place
+        edit: the version counters show it) or the storage type changed, the features are computed again from the kept
+        pixels and the object is updated in place.  NOT noticed: weights written in place into the SAME tower object (the
+        frozen tower is compared by identity only) -- encode again after such a load.  ValueError under grad with trainable
+        parameters."""
+        self._refuse_under_grad()
+        with torch.no_grad():
+            self._maybe_prepare()
+            if enc.tower is not self.vision_tower[0] or enc.dtype != self.dtype or \
+                    enc.spi_stamp != self.spi_module._param_stamp() or enc.proj_stamp != self._proj_stamp():
+                enc.tokens, enc.maps, enc.affs, enc.P = self._encode(enc.pixels[None])
+                enc.image_size, enc.dtype, enc.tower = 14 * enc.P, self.dtype, self.vision_tower[0]
+                enc.spi_stamp, enc.proj_stamp = self.spi_module._param_stamp(), self._proj_stamp()
+                enc.encodes += 1
+        return enc.tokens, enc.maps, enc.affs
+
+    def embed_window(self, input_ids, encs, image_of_row=None, bboxes=None, lo=None, hi=None, region_from=None):
+        """The sibling of `embed_inputs` for images that are already encoded: -> the window [B, W, C] of the spliced
+        embeddings, row b's positions [lo[b], hi[b]) in slots [0, hi[b] - lo[b]) and zeros behind (W = the widest window,
+        at least 1); `last_status` is set as embed_inputs sets it (over the WHOLE rows).
+        encs: an EncodedImage or a list of U of them; image_of_row[b] says which one row b shows (default: the one, or
+        row b's own when U = B).  bboxes: None or the list of B [n_b, 4] tensors of the reference (ALL boxes of every
+        row).  lo / hi: ints or lists of B ints, default the whole rows.  region_from[b] (default: the number of `<bbox>`
+        tokens before lo[b], generation.plan_windows): the ordinal of row b's first box that goes through the region head
+        -- the earlier ones belong to positions before the window, whose embeddings somebody else holds.  The region
+        head runs once per image, over the boxes of all rows that show it, pooled from that image's cached maps; not at
+        all when no box is left.  One windowed splice (kernels.splice_embed_window) follows."""
+        self._refuse_under_grad()
+        with torch.no_grad():
+            return self._embed_window(input_ids, encs, image_of_row, bboxes, lo, hi, region_from)
+
+    def _embed_window(self, input_ids, encs, image_of_row, bboxes, lo, hi, region_from):
+        cfg = self.config
+        B, T = input_ids.shape
+        encs = [encs] if is_encoded(encs) else list(encs)
+        U = len(encs)
+        if image_of_row is None:
+            if U not in (1, B):
+                raise ValueError(f"{U} encoded images for {B} rows: image_of_row= has to say which row shows which")
+            image_of_row = [0] * B if U == 1 else list(range(B))
+        image_of_row = [int(u) for u in image_of_row]
+        if len(image_of_row) != B or any(not 0 <= u < U for u in image_of_row):
+            raise ValueError(f"image_of_row = {image_of_row}: {B} indices into {U} encoded images wanted")
+        if len({(e.image_size, e.dtype) for e in encs}) != 1:
+            raise ValueError("the encoded images of one batch must share the image size and the storage type")
+        feats = [self.features_of(e) for e in encs]
+        if isinstance(bboxes, PreparedBoxes):
+            raise ValueError("embed_window reads the boxes as a list of [n, 4] tensors, one per row (it selects among them)")
+        if bboxes is not None and len(bboxes) == 0:
+            bboxes = None
+        if bboxes is not None and len(bboxes) != B:
+            raise ValueError(f"{len(bboxes)} box lists for {B} rows")
+        if lo is None and hi is None and region_from is None:
+            lo, hi, region_from = [0] * B, [T] * B, [0] * B
+        elif region_from is None:                  # the one case that has to look at the ids on the host
+            plan = plan_windows(input_ids.tolist(), 0 if lo is None else lo, T if hi is None else hi, cfg.bbox_token)
+            lo, hi, region_from = plan.lo, plan.hi, plan.region_from
+        else:                                      # a planned call (generation.plan_*): bounds against T, no host read
+            plan = plan_windows([range(T)] * B, 0 if lo is None else lo, T if hi is None else hi, None)
+            lo, hi, region_from = plan.lo, plan.hi, [int(k) for k in region_from]
+        if len(region_from) != B or any(k < 0 for k in region_from):
+            raise ValueError(f"region_from = {region_from}: {B} ordinals >= 0 wanted")
+        dev = input_ids.device
+        spi, off = None, None
+        if bboxes is not None:
+            rest = [bboxes[b][region_from[b]:] for b in range(B)]
+            per_row = [None] * B
+            for u in range(U):
+                rows = [b for b in range(B) if image_of_row[b] == u]
+                if sum(int(rest[b].size(0)) for b in rows) == 0:
+                    continue
+                prep = PreparedBoxes([rest[b] for b in rows], encs[u].image_size, dev, dtype=self.dtype,
+                                     image_of_row=[0] * len(rows))
+                for b, f in zip(rows, self.spi_module.extract(feats[u][1], feats[u][2], prep)):
+                    per_row[b] = f
+            have = [f for f in per_row if f is not None and f.size(0) > 0]
+            if have:
+                spi = have[0] if len(have) == 1 else torch.cat(have, 0).contiguous()
+            counts, o = [int(r.size(0)) for r in rest], [0]
+            for c in counts:
+                o.append(o[-1] + c)
+            off = torch.tensor(o, dtype=torch.int32).to(dev)
+        img = feats[0][0][None] if U == 1 else torch.stack([f[0] for f in feats], 0)
+        W = max([1] + [z - a for a, z in zip(lo, hi)])
+        out, status = K.splice_embed_window(input_ids.contiguous(), self.llama.embed, img, image_of_row, spi, off, region_from,
+                                            lo, hi, W, img.size(1), cfg.im_patch_token, cfg.bbox_token, cfg.im_start_token,
+                                            cfg.im_end_token)
+        self.last_status = status
+        return out
 
     def prepare_boxes(self, bboxes, image_size):
         """Do the host-side part of a request once (see layers.PreparedBoxes); the returned object can be
@@ -330,6 +466,9 @@ class SPILlavaLlamaModel(nn.Module):
                 raise ValueError('The image end token should follow the image start token.')
             if any(c & 2 for c in codes):
                 raise ValueError('The number of <bbox> tokens does not match the number of regions.')
+            if any(c & 32 for c in codes):
+                raise ValueError('A <bbox> token inside the spliced window has no region feature (it was counted among the '
+                                 'boxes before the window).')
             raise ValueError(f'malformed multimodal prompt (status {codes})')
 
     # ---- training rows: the forward that keeps what the backward needs, and that backward ----------------------
@@ -422,6 +561,8 @@ class SPILlavaLlamaModel(nn.Module):
                 use_cache: Optional[bool] = None, output_attentions: Optional[bool] = None,
                 output_hidden_states: Optional[bool] = None, images: Optional[torch.Tensor] = None,
                 return_dict: Optional[bool] = None, all_logits=True):
+        if is_encoded(images) or (isinstance(images, (list, tuple)) and any(is_encoded(i) for i in images)):
+            self._refuse_under_grad()
         if torch.is_grad_enabled() and inputs_embeds is None and images is not None and input_ids.size(1) != 1:
             named = self.trainable_named()
             if named:
@@ -613,7 +754,7 @@ class SPILlavaMPTForCausalLM(nn.Module):
     def generate(self, input_ids=None, images=None, max_new_tokens=64, do_sample=None, temperature=None, top_k=None,
                  top_p=None, stopping_criteria=None, eos_token_id=None, seed=None, bboxes=None, stop_ids=(),
                  check_every=None, return_new_tokens=False, attention_mask=None, pad_token_id=None, session=None,
-                 shared_prefix=None, num_return_sequences=None, **_):
+                 shared_prefix=None, num_return_sequences=None, share_images=False, **_):
         """HF-style `generate`.  Batch 1 (what gpt4roi/app.py:293-300 calls): prefill through `self.forward` -- so a
         `partial(orig_forward, img_metas=..., bboxes=...)` bound by the caller is honoured (app.py:286-291; `bboxes=`
         may also be passed here) -- then the device-resident decode loop.  do_sample=False: greedy (the parity mode);
@@ -645,10 +786,27 @@ class SPILlavaMPTForCausalLM(nn.Module):
         num_return_sequences = n > 1 (batch 1, do_sample=True): n samples of the ONE prompt through the shared path with
         P = T - 1; `seed` expands over the n rows like a batch's (generation.expand_seeds).  Returns [n, T + longest] padded
         with pad_token_id (or a list of n id lists with return_new_tokens).  ValueError with greedy decoding (n equal rows,
-        as in HF), with B > 1 and with session=.  The vision path still runs per row."""
+        as in HF), with B > 1 and with session=.  The vision path runs once for the n rows with share_images=True or an
+        EncodedImage, else per row.
+        images may also be an EncodedImage (SPILlavaLlamaModel.encode_image) or a list of B entries, each an EncodedImage or
+        a [3, S, S] tensor; repeated objects (or equal pixels) are repeated images.  An encoded image runs no ViT and no
+        fuse round: batch 1 splices the whole prompt from it (embed_window over [0, T)) and is otherwise the call above.
+        share_images=True (with shared_prefix= or num_return_sequences > 1; default False): the rows are grouped by image
+        (generation.group_images), each distinct image is encoded ONCE at batch 1, the prefix [0, P) is spliced once from
+        row 0 and only every row's suffix [P, n_b) at batch B (generation.plan_shared_windows) -- the [B, T, C] embedding
+        tensor of the default path is never built, and the boxes of the prefix go through the region head once.  Images
+        that arrive encoded take this path without the flag.  session=GenerationSession(cache_image=True): the session
+        keeps the picture's EncodedImage; a turn on the same image runs no ViT and no fuse round, splices only the
+        positions [L, T) it prefills and runs the region head only for the boxes whose `<bbox>` lies there."""
         n_ret = 1 if num_return_sequences is None else int(num_return_sequences)
         if n_ret < 1:
             raise ValueError(f"num_return_sequences = {num_return_sequences}: has to be >= 1")
+        if share_images and n_ret == 1 and (shared_prefix is None or shared_prefix is False):
+            raise ValueError("share_images=True encodes the images of a shared-prefix batch once: pass shared_prefix=True "
+                             "(or num_return_sequences=n)")
+        encoded = self._check_images(images, input_ids.size(0))
+        if encoded and getattr(self, "model", None) is not None:
+            self._check_patch_count(input_ids, images)
         if n_ret > 1:
             if input_ids.size(0) > 1:
                 raise ValueError("num_return_sequences > 1 takes ONE prompt; got a batch of "
@@ -665,7 +823,7 @@ class SPILlavaMPTForCausalLM(nn.Module):
                 raise ValueError("num_return_sequences > 1 needs a prompt of at least 2 tokens")
             return self._generate_batch(input_ids, images, max_new_tokens, do_sample, temperature, top_k, top_p, seed,
                                         stopping_criteria, eos_token_id, bboxes, stop_ids, check_every, return_new_tokens,
-                                        attention_mask, pad_token_id, copies=n_ret)
+                                        attention_mask, pad_token_id, copies=n_ret, share_images=share_images or encoded)
         if shared_prefix is not None and shared_prefix is not False and input_ids.size(0) == 1:
             raise ValueError("shared_prefix= is for a batch (B > 1); one prompt with n samples: num_return_sequences=n")
         if session is not None and input_ids.size(0) > 1:
@@ -674,7 +832,8 @@ class SPILlavaMPTForCausalLM(nn.Module):
         if input_ids.size(0) > 1:
             return self._generate_batch(input_ids, images, max_new_tokens, do_sample, temperature, top_k, top_p, seed,
                                         stopping_criteria, eos_token_id, bboxes, stop_ids, check_every, return_new_tokens,
-                                        attention_mask, pad_token_id, shared_prefix=shared_prefix)
+                                        attention_mask, pad_token_id, shared_prefix=shared_prefix,
+                                        share_images=share_images or encoded)
         if isinstance(seed, (list, tuple)):
             if len(seed) != 1:
                 raise ValueError(f"{len(seed)} seeds for a batch of 1 sequence")
@@ -692,7 +851,8 @@ class SPILlavaMPTForCausalLM(nn.Module):
         dec = self.model.llama
         # step 0 = prefill through the (possibly partial-bound) forward; only its embeddings are needed here: the
         # decode loop owns the KV cache, so hand it the spliced embeddings
-        embeds = self._prefill_embeds(fwd, model_inputs, kw)
+        cached = session is not None and getattr(session, "cache_image", False) and images is not None
+        embeds = None if cached else self._prefill_embeds(fwd, model_inputs, kw)
         stops = set(int(s) for s in stop_ids)
         if eos_token_id is None:                            # HF generate stops on the config's EOS id by default
             eos_token_id = getattr(self.config, "eos_token_id", None)
@@ -715,9 +875,20 @@ class SPILlavaMPTForCausalLM(nn.Module):
             bound = getattr(fwd, "keywords", None) or {}
             boxes = _box_rows(kw.get("bboxes", bound.get("bboxes")))
             prompt_ids = input_ids[0].tolist()
+            if cached:
+                # the session's encoding when the turn shows its image (no ViT, no fuse round), else a new one; then only
+                # the positions the decoder will prefill are spliced, with the region head on the boxes that sit there
+                if session.same_image(images) and is_encoded(session.image):
+                    images = session.image
+                else:
+                    images = self.model.encode_image(images)
             past = session.plan(dec, prompt_ids, images, boxes, self.model.config.bbox_token, max_new_tokens)
+            if cached:
+                win = plan_session_window(prompt_ids, past, self.model.config.bbox_token)
+                embeds = self.model.embed_window(input_ids, images, [0], kw.get("bboxes", bound.get("bboxes")), win.lo, win.hi,
+                                                 win.region_from)
         new = dec.decode_graph(embeds, max_new_tokens, stop_ids=stops, check_every=every, sampler=sampler, seed=seed,
-                               on_tokens=on_tokens, past_len=past)
+                               on_tokens=on_tokens, past_len=past, embeds_from=past if cached else 0)
         if session is not None:
             session.update(dec, prompt_ids, new, images, boxes, past)
         if return_new_tokens:
@@ -726,8 +897,9 @@ class SPILlavaMPTForCausalLM(nn.Module):
 
     def _generate_batch(self, input_ids, images, max_new_tokens, do_sample, temperature, top_k, top_p, seed,
                         stopping_criteria, eos_token_id, bboxes, stop_ids, check_every, return_new_tokens, attention_mask,
-                        pad_token_id, shared_prefix=None, copies=1):
-        """copies = n > 1: the ONE prompt row is served n times through the shared-prefix path (num_return_sequences)."""
+                        pad_token_id, shared_prefix=None, copies=1, share_images=False):
+        """copies = n > 1: the ONE prompt row is served n times through the shared-prefix path (num_return_sequences).
+        share_images (shared path only): the images are encoded once each and the prefix / suffix blocks spliced apart."""
         B = input_ids.size(0) if copies == 1 else copies
         if shared_prefix is False:
             shared_prefix = None
@@ -748,14 +920,17 @@ class SPILlavaMPTForCausalLM(nn.Module):
         sampler = cfg.sampler()
         seeds = expand_seeds(seed, B) if sampler is not None else None      # (validates a list's length before any work)
         kw = dict(bboxes=bboxes) if bboxes is not None else {}
-        P = None
+        P = host_ids = None
         if copies > 1:
             P = input_ids.size(1) - 1                       # n rows of one prompt: everything but the last position
         elif shared_prefix is not None:
             bound = getattr(self.forward, "keywords", None) or {}
             boxes = _batch_box_rows(kw.get("bboxes", bound.get("bboxes")), B)
-            same = images is None or all(bool(torch.equal(images[b], images[0])) for b in range(1, B))
-            ids = input_ids.tolist()
+            if images is None or isinstance(images, torch.Tensor):
+                same = images is None or all(bool(torch.equal(images[b], images[0])) for b in range(1, B))
+            else:
+                same = all(same_pixels(images[b], images[0]) for b in range(1, B))
+            ids = host_ids = input_ids.tolist()
             bbox_id = getattr(getattr(getattr(self, "model", None), "config", None), "bbox_token", None)
             plan = plan_shared_prefix([ids[b][:lens[b]] for b in range(B)], same, boxes, bbox_id)
             if shared_prefix is True:
@@ -766,11 +941,20 @@ class SPILlavaMPTForCausalLM(nn.Module):
             else:
                 P = int(shared_prefix)
         self.last_shared_prefix = P                         # what the last batched call planned (None: the masked batch)
-        embeds = self._prefill_embeds(self.forward, self.prepare_inputs_for_generation(input_ids, images=images), kw)
-        if copies > 1:
-            embeds = embeds.expand(copies, -1, -1)
-            input_ids = input_ids.expand(copies, -1)
-            attention_mask = None
+        prefix_embeds = None
+        if share_images and P is not None and images is not None:
+            if copies > 1:
+                host_ids = input_ids.tolist() * copies
+                input_ids = input_ids.expand(copies, -1)
+                attention_mask = None
+            embeds, prefix_embeds, attention_mask = self._shared_image_embeds(input_ids, images, kw, P, lens, attention_mask,
+                                                                             copies, host_ids)
+        else:
+            embeds = self._prefill_embeds(self.forward, self.prepare_inputs_for_generation(input_ids, images=images), kw)
+            if copies > 1:
+                embeds = embeds.expand(copies, -1, -1)
+                input_ids = input_ids.expand(copies, -1)
+                attention_mask = None
         stops = set(int(s) for s in stop_ids)
         if eos_token_id is None:
             eos_token_id = getattr(self.config, "eos_token_id", None)
@@ -788,13 +972,71 @@ class SPILlavaMPTForCausalLM(nn.Module):
         every = check_every if check_every is not None else (1 if stopping_criteria else 32)
         new = self.model.llama.decode_graph_batch(embeds, max_new_tokens, stop_ids=stops, key_padding_mask=attention_mask,
                                                   sampler=sampler, seeds=seeds, on_tokens=on_tokens, check_every=every,
-                                                  shared_prefix=P, own_positions=None if P is None else True)
+                                                  shared_prefix=P, own_positions=None if P is None else True,
+                                                  prefix_embeds=prefix_embeds)
         if return_new_tokens:
             return new
         pad = pad_token_id if pad_token_id is not None else (getattr(self.config, "pad_token_id", None) or 0)
         n = max(len(r) for r in new)
         tail = torch.tensor([r + [pad] * (n - len(r)) for r in new], dtype=input_ids.dtype, device=input_ids.device)
         return torch.cat([input_ids, tail], 1)
+
+    def _check_images(self, images, B):
+        """`images` of a generate() call, looked at before the model is touched: -> whether any row arrives as an
+        EncodedImage.  ValueError for a list that does not have one entry per row and for images (encoded or not) of
+        different sizes; `_check_patch_count` then holds an encoding against the prompt."""
+        if images is None or (isinstance(images, torch.Tensor) and not is_encoded(images)):
+            return False
+        rows = [images] if is_encoded(images) else list(images)
+        if len(rows) != B:
+            raise ValueError(f"{len(rows)} images for a batch of {B} sequences")
+        sizes = {int(r.image_size) if is_encoded(r) else int(r.size(-1)) for r in rows}
+        if len(sizes) != 1:
+            raise ValueError(f"the images of one call must have one size, got {sorted(sizes)}")
+        return any(is_encoded(r) for r in rows)
+
+    def _check_patch_count(self, input_ids, images):
+        """An encoded image must bring as many patch tokens as the prompt has `<im_patch>` ids (one small host read)."""
+        enc = next((r for r in ([images] if is_encoded(images) else list(images)) if is_encoded(r)), None)
+        n = int((input_ids[0] == self.model.config.im_patch_token).sum())
+        if enc is not None and n not in (0, int(enc.tokens.size(0))):
+            raise ValueError(f"the prompt holds {n} <im_patch> tokens, the EncodedImage ({enc.image_size} x {enc.image_size}) "
+                             f"brings {int(enc.tokens.size(0))}: it was encoded at another image size")
+
+    def _shared_image_embeds(self, input_ids, images, kw, P, lens, attention_mask, copies, host_ids):
+        """The embeddings of a shared-prefix batch with every distinct image encoded once: -> (suffix block [B, T - P, C],
+        prefix block [1, P, C] or None when P = 0, the mask cut to the T = max n_b columns that hold a real token)."""
+        model = self.model
+        B = input_ids.size(0)
+        bound = getattr(self.forward, "keywords", None) or {}
+        bboxes = kw.get("bboxes", bound.get("bboxes"))
+        if bboxes is not None and len(bboxes) == 0:
+            bboxes = None
+        if copies > 1:
+            rows = [images if is_encoded(images) else images[0]] * copies if not isinstance(images, (list, tuple)) \
+                else list(images) * copies
+            if bboxes is not None:
+                bboxes = list(bboxes) * copies
+        else:
+            rows = images
+        uniq, image_of_row = group_images(rows)
+        encs = [model.encode_image(u) for u in uniq]
+        T = max(lens)
+        ids = input_ids[:, :T].contiguous()
+        if attention_mask is not None:
+            attention_mask = attention_mask[:, :T]
+        real = [host_ids[b][:lens[b]] for b in range(B)]          # (the host copy _generate_batch already made)
+        bbox_id = model.config.bbox_token
+        if P == 0:
+            win = plan_windows(real, 0, None, bbox_id)
+            return model.embed_window(ids, encs, image_of_row, bboxes, win.lo, win.hi, win.region_from), None, attention_mask
+        pre, suf = plan_shared_windows(real, P, bbox_id)
+        prefix = model.embed_window(ids[:1], encs[image_of_row[0]], [0], None if bboxes is None else bboxes[:1], pre.lo,
+                                    pre.hi, pre.region_from)
+        st0 = model.last_status
+        suffix = model.embed_window(ids, encs, image_of_row, bboxes, suf.lo, suf.hi, suf.region_from)
+        model.last_status[:1] |= st0                         # one status per row, as embed_inputs leaves it
+        return suffix, prefix, attention_mask
 
     def _prefill_embeds(self, fwd, model_inputs, kw):
         """The spliced prompt embeddings of step 0.  When `forward` was rebound with partial(bboxes=...) the boxes live

@@ -41,6 +41,7 @@
 #define g4r_rope_qkv_bf16                   g4r_rope_qkv_f16
 #define g4r_swiglu_bf16                     g4r_swiglu_f16
 #define g4r_splice_embed_bf16               g4r_splice_embed_f16
+#define g4r_splice_embed_window_bf16        g4r_splice_embed_window_f16
 #define g4r_add_rows_bf16                   g4r_add_rows_f16
 #define g4r_cast_f32_to_bf16                g4r_cast_f32_to_f16
 #define g4r_conv3x3_weight_layout_bf16      g4r_conv3x3_weight_layout_f16

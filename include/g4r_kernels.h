@@ -280,6 +280,20 @@ int g4r_splice_embed_bf16(const long* ids, const void* embed, const void* img, c
                           const int* spi_offset, void* out, int* status, int B, int T, int C,
                           int n_patch, long patch_id, long bbox_id, long im_start_id, long im_end_id,
                           int vocab, void* stream);
+/*
+ * The windowed sibling of g4r_splice_embed_bf16: sample b writes only its positions [lo[b], hi[b]) into the compact
+ * out [B, W, C] (slot j = position lo[b] + j; slots j >= hi[b] - lo[b] are zeros; W >= max(hi - lo), W >= 1) and takes
+ * its patch rows from img[img_of_row[b]], img being [n_img, n_patch, C].  spi_skip[b] leading <bbox> tokens of sample b
+ * have NO row in `spi` (their positions lie before the window): the <bbox> of rank r reads
+ * spi[spi_offset[b] + r - spi_skip[b]].  img_of_row, spi_skip, lo, hi: device int32 [B], 0 <= lo <= hi <= T (clamped on
+ * the device; the caller checks them where their values are known).  status[b]: the bits above, computed over the
+ * WHOLE row; bit 2 is #<bbox> != spi_skip[b] + #regions; 32 = a <bbox> inside the window with rank < spi_skip[b].
+ */
+int g4r_splice_embed_window_bf16(const long* ids, const void* embed, const void* img, const int* img_of_row,
+                                 const void* spi, const int* spi_offset, const int* spi_skip, const int* lo,
+                                 const int* hi, void* out, int* status, int B, int T, int W, int C, int n_patch,
+                                 int n_img, long patch_id, long bbox_id, long im_start_id, long im_end_id, int vocab,
+                                 void* stream);
 
 /* Device-side greedy step: tok = argmax(logits[:N]); out_ids[*step] = tok; ++*step; ++*pos  (nothing
  * returns to the host, so generate(do_sample=False)'s per-token loop -- llava.py:263-283, app.py:294-300
